@@ -8,6 +8,9 @@ RSGAN + zero-centred GP (lambda 0.5), Adam(2e-4, (0.5, 0.999)), 1 D step + 1 G s
 --subsample_input pyramid 8/16/32/64; synthetic Moving-MNIST-shaped batches resident in HBM.
 One "step" = one full iteration of txt2vid_amd.gan.trainer.train_iteration (G fwd, D loss + GP double
 backward, Adam, real_pred, G loss backward through D, Adam). Prints ONE JSON line on rank 0.
+
+    --dump-outputs DIR   after the timed steps, rank 0 writes what the last of them computed as DIR/<name>.npy (see
+                         dump_outputs); models, batches and random draws are seeded, so equal arguments give equal inputs
 """
 import argparse
 import ctypes as C
@@ -283,6 +286,56 @@ class _Run(object):
     pass
 
 
+DUMP_BUDGET = 64 << 20           # bytes, all files of --dump-outputs together
+DUMP_MAX_ELEMS = 1 << 21         # per array; a larger one is written as a fixed, seeded sample of this many elements
+
+
+def _flat_sample(tensors, seed):
+    """The elements of `tensors` (read as one flat vector, in order) as a float host array: all of them, or DUMP_MAX_ELEMS at
+    positions drawn from a generator seeded by `seed` and the total size alone (the same positions in every run)."""
+    n = sum(t.numel() for t in tensors)
+    if n <= DUMP_MAX_ELEMS:
+        return np.concatenate([t.detach().reshape(-1).cpu().numpy() for t in tensors])
+    idx = np.sort(np.random.default_rng([seed, n]).integers(0, n, size=DUMP_MAX_ELEMS))
+    offs = np.cumsum([0] + [t.numel() for t in tensors])
+    parts = []
+    for t, lo, hi in zip(tensors, offs[:-1], offs[1:]):
+        a, b = np.searchsorted(idx, lo), np.searchsorted(idx, hi)
+        if b > a:
+            sel = torch.from_numpy(idx[a:b] - lo).to(t.device)
+            parts.append(t.detach().reshape(-1)[sel].cpu().numpy())
+    return np.concatenate(parts)
+
+
+def dump_outputs(out_dir, gan, last):
+    """`--dump-outputs DIR`: what the last timed step computed, as DIR/<name>.npy — the two losses, the generated videos of
+    every pyramid level, the updated G and D weights (a seeded sample: ~115 M values) and, in float64, the sum and the sum of
+    squares of every weight tensor (which sees every element). Returns the names written."""
+    arrays = {'lossD': [last['lossD']], 'lossG': [last['lossG']]}
+    for i, f in enumerate(last['fake']):
+        arrays['fake_%d' % i] = [f]
+    for tag, models in (('G', [gan.gen]), ('D', gan.discrims)):
+        params = [p for m in models for p in m.parameters()]
+        arrays['%s_params' % tag] = params
+        arrays['%s_param_stats' % tag] = torch.stack([torch.stack([p.detach().double().sum(), p.detach().double().square().sum()])
+                                                      for p in params])
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for seed, name in enumerate(sorted(arrays)):
+        v = arrays[name]
+        if torch.is_tensor(v):
+            a = v.detach().cpu().numpy()
+        else:
+            a = _flat_sample(v, seed)
+            a = a.reshape(v[0].shape) if len(v) == 1 and a.size == v[0].numel() else a
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        if total > DUMP_BUDGET:
+            raise RuntimeError('--dump-outputs: over %d bytes at %s' % (DUMP_BUDGET, name))
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
+
+
 def timed_run(args, cond, size, channels, steps, warmup, rank, world, dev, log, prof_eager=False):
     """Build the models of one workload (current conv precision), warm up (2 eager iterations + graph capture), then time exactly
     `steps` iterations between barrier + synchronize pairs. Returns the objects the roofline passes need plus `dt` (this rank's
@@ -358,7 +411,7 @@ def timed_run(args, cond, size, channels, steps, warmup, rank, world, dev, log, 
         grad_sync.time_exchanges(True)
     t0 = time.perf_counter()
     for i in range(steps):
-        lD, lG, _, _ = step(warmup + i)
+        lD, lG, fake, _ = step(warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -368,6 +421,7 @@ def timed_run(args, cond, size, channels, steps, warmup, rank, world, dev, log, 
     if grad_sync is not None:
         R.exchange = grad_sync.exchange_ms()
         grad_sync.time_exchanges(False)
+    R.last = {'lossD': lD, 'lossG': lG, 'fake': graphed.ts.fake if graphed is not None else fake}     # the last timed step's results
     R.lD, R.lG = float(lD), float(lG)
     R.gan, R.optD, R.optG, R.losses, R.prm, R.pool, R.graphed, R.grad_sync, R.txt = gan, optD, optG, losses, prm, pool, graphed, grad_sync, txt
     R.sentence_codes, R.warmup = sentence_codes, warmup
@@ -393,7 +447,11 @@ def main():
     ap.add_argument('--channels', type=int, default=1, choices=(1, 3))
     ap.add_argument('--no_hbm', action='store_true', help='skip the HBM-bound kernels block')
     ap.add_argument('--no_extra', action='store_true', help='skip the extra BASELINE configs[2] record (text-conditioned, bf16 compute) of the default run')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (losses, generated '
+                                                          'videos, a seeded sample of the updated weights; at most 64 MB)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` (no launcher): start the N ranks as a CHILD torch.distributed.run — nothing in this
@@ -432,6 +490,10 @@ def main():
     sentence_codes, dt, lD, lG, prof_in_region = R.sentence_codes, R.dt, R.lD, R.lG, R.prof_in_region
     from txt2vid_amd.gan.trainer import train_iteration
     log('timed region done: %.1f ms/step' % (dt / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:          # before the instrumented eager pass below updates the weights again
+        names = dump_outputs(args.dump_outputs, gan, R.last)
+        log('outputs of the last timed step written to %s: %s' % (args.dump_outputs, ' '.join(names)))
+    R.last = None
     lD, lG = float(lD), float(lG)
     roof = None
     prof_steps, prof_dt = args.steps, dt

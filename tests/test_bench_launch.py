@@ -40,3 +40,34 @@ def test_bare_multi_gpu_invocation_goes_through_self_launch(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert e.value.code == 5
+
+
+def test_dump_outputs_writes_the_last_step_within_budget(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: losses, generated videos and weights as float .npy files; an array over the per-array cap is a seeded
+    sample (the same positions in every run), the stats see every weight, and the total stays under the budget."""
+    sys.path.insert(0, ROOT)
+    import types
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_MAX_ELEMS', 1000)
+    torch.manual_seed(0)
+    gen, dis = torch.nn.Linear(40, 50), torch.nn.Conv3d(2, 3, 3)
+    gan = types.SimpleNamespace(gen=gen, discrims=[dis])
+    last = {'lossD': torch.tensor(0.5), 'lossG': torch.tensor(1.25),
+            'fake': [torch.randn(2, 1, 4, 8, 8, requires_grad=True), torch.randn(2, 1, 16, 16, 16)]}
+    names = bench.dump_outputs(str(tmp_path / 'a'), gan, last)
+    bench.dump_outputs(str(tmp_path / 'b'), gan, last)
+    assert names == sorted(['lossD', 'lossG', 'fake_0', 'fake_1', 'G_params', 'D_params', 'G_param_stats', 'D_param_stats'])
+    a = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in names}
+    for n in names:
+        assert a[n].dtype in (np.float32, np.float64)
+        assert np.array_equal(a[n], np.load(str(tmp_path / 'b' / (n + '.npy'))))
+    assert a['lossD'].shape == () and a['lossD'] == np.float32(0.5) and a['lossG'] == np.float32(1.25)
+    assert np.array_equal(a['fake_0'], last['fake'][0].detach().numpy())                     # 512 values: written whole
+    assert a['fake_1'].shape == (1000,) and np.isin(a['fake_1'], last['fake'][1].numpy()).all()  # 8192 values: a sample
+    assert a['G_params'].shape == (1000,) and a['D_params'].shape == (dis.weight.numel() + dis.bias.numel(),)
+    assert np.array_equal(a['D_params'], np.concatenate([dis.weight.detach().reshape(-1).numpy(), dis.bias.detach().numpy()]))
+    assert a['G_param_stats'].dtype == np.float64 and a['G_param_stats'].shape == (2, 2)
+    assert np.isclose(a['G_param_stats'][0, 0], gen.weight.double().sum().item())
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_BUDGET
