@@ -565,6 +565,26 @@ int t2v_nonlocal_fwd(const float* theta, const float* phi, const float* g, float
 int t2v_nonlocal_bwd(const float* theta, const float* phi, const float* g, const float* o, const float* lse, const float* go,
                      float* dtheta, float* dphi, float* dg, float* ws, int b, int C8, int C2, int N, int Nk, void* stream);
 
+
+/* ---- TGAN-v1 frame-seed generator of MultiScaleGen(no_lstm=True) (txt2vid/models/tgan/temporal_gen.py:10-34) ----------------
+ * Activations [B, C, L]; weights [Cin, Cout, K] (torch ConvTranspose1d); K = 1 (Lin = 1) or K = 4, stride 2, padding 1
+ * (Lin in {1, 2, 4, 8}, Lout = 2 Lin). fp32 only.
+ * t2v_tseed_fwd_bn: y = convT(relu(x * scale_in + shift_in), w) + bias ([B, Cout, Lout], before its BatchNorm); ss_in points
+ *   at (scale[Cin], shift[Cin]) of the BatchNorm in front of the layer, or is null (dc0: x used as is). training = 1: the
+ *   batch statistics of y -> st = [mean | 1/std | scale | shift] (4*Cout floats), running buffers and the step counter
+ *   updated in the same launch; training = 0: st's scale / shift from the running buffers. Cin*K <= 16384.
+ * t2v_tseed_fwd_tanh: z = tanh(convT(relu(x * scale_in + shift_in), w) + bias), Lin = 8: z [B, Cout, 16].
+ * t2v_tseed_bwd: g = dL/dy [B, Cout, Lout] (flags & 1: dL/dz of the tanh layer, z given). dw [Cin, Cout, K], db [Cout];
+ *   gin (may be null) = dL/dx — through the ReLU + BatchNorm in front when st_in (that layer's st) is given, which also
+ *   yields its dgamma / dbeta. flags 2 / 4 / 8 / 16: add into dw / db / dgamma / dbeta instead of storing. */
+int t2v_tseed_fwd_bn(const float* x, const float* ss_in, const float* w, const float* bias, const float* gamma, const float* beta,
+                     float* y, float* st, float* running_mean, float* running_var, int64_t* batches_tracked, int B, int Cin,
+                     int Cout, int Lin, int K, float momentum, float eps, int training, void* stream);
+int t2v_tseed_fwd_tanh(const float* x, const float* ss_in, const float* w, const float* bias, float* z, int B, int Cin, int Cout,
+                       int Lin, void* stream);
+int t2v_tseed_bwd(const float* g, const float* z, const float* w, const float* a_in, const float* st_in, float* gin, float* dw,
+                  float* db, float* dgamma, float* dbeta, int B, int Cin, int Cout, int Lin, int K, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

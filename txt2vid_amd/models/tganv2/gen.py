@@ -7,6 +7,7 @@ import torch.nn as nn
 from .. import layers as L
 from ..layers import UpBlock, RenderBlock, Subsample, Linear
 from ..conv_lstm import ConvLSTM
+from ..tgan.temporal_gen import FrameSeedGenerator
 
 
 class BaseFrameGen(nn.Module):
@@ -32,17 +33,19 @@ class MultiScaleGen(nn.Module):
     def __init__(self, latent_size=256, width=128, height=128, num_channels=3, additional_blocks=[64, 32, 32],
                  fm_channels=1024, num_frames=16, cond_dim=0, no_lstm=False):
         super().__init__()
-        if no_lstm:
-            raise NotImplementedError('no_lstm (TGAN-v1 frame seed generator) is outside the hot path')
-        self.no_lstm = False
         self.subsample = Subsample()
         # the recurrent state is a [fm_channels, height/64, width/64] map per sample: 1x1 for 64x64 frames, 2x2 for 128x128
         self.latent_size, self.fm_channels, self.latent_plane_ch = latent_size, fm_channels, fm_channels
         self.fm_width, self.fm_height = max(1, width // 64), max(1, height // 64)
         self.fm_size = self.latent_plane_ch * self.fm_height * self.fm_width
         self.fc = Linear(latent_size + (cond_dim if self._cond_variant else 0), self.fm_size)
-        self.clstm = ConvLSTM(input_channels=fm_channels, hidden_channels=[fm_channels], kernel_size=3, step=num_frames,
-                              effective_step=range(num_frames))
+        self.no_lstm = no_lstm
+        if no_lstm:
+            # TGAN-v1's frame-seed generator instead of the ConvLSTM: always 16 frames, whatever num_frames says (gen.py:40-43)
+            self.frame_seed_gen = FrameSeedGenerator(self.fm_size, self.fm_size)
+        else:
+            self.clstm = ConvLSTM(input_channels=fm_channels, hidden_channels=[fm_channels], kernel_size=3, step=num_frames,
+                                  effective_step=range(num_frames))
         # level 0 = BaseFrameGen (-> 128 channels), then one UpBlock per entry of additional_blocks; a RenderBlock per level.
         # The text-conditioned variant puts its 2-D non-local block into the last-but-one UpBlock.
         widths = [128] + list(additional_blocks)
@@ -58,7 +61,7 @@ class MultiScaleGen(nn.Module):
         """{weight: live kernel taps} for the ConvLSTM when its state is 1x1 (frames below 128x128): a 3x3 kernel on a 1x1
         map only ever multiplies — and only ever receives a gradient through — its centre tap. Used by `dist.model_arena`:
         8 x [1024,1024,3,3] weights = 302 MB of gradients of which 33.5 MB can be non-zero."""
-        if self.fm_width != 1 or self.fm_height != 1:
+        if self.no_lstm or self.fm_width != 1 or self.fm_height != 1:
             return {}
         cell = self.clstm.cell0
         k = cell.kernel_size
@@ -70,10 +73,17 @@ class MultiScaleGen(nn.Module):
         if cond is not None:
             x = TF.cat_features(x, cond)
         x = self.fc(x)
-        x = x.view(x.size(0), self.latent_plane_ch, self.fm_height, self.fm_width)
-        hs = self.clstm.forward_stacked(x)                     # [T,B,C,h,w]
-        num_frames = hs.size(0)
-        x = TF.time_to_batch(hs)                               # [B*T,C,h,w]  (stack+permute+merge_frames)
+        if self.no_lstm:
+            # [B, fm, 16] contiguous; the reference's view(B, 16, -1, h, w) + merge_frames reinterprets that memory as
+            # [B*16, C, h, w] (channels and frames scrambled on purpose: no permute)
+            x = self.frame_seed_gen(x)
+            num_frames = 16
+            x = x.view(x.size(0) * num_frames, -1, self.fm_height, self.fm_width)
+        else:
+            x = x.view(x.size(0), self.latent_plane_ch, self.fm_height, self.fm_width)
+            hs = self.clstm.forward_stacked(x)                 # [T,B,C,h,w]
+            num_frames = hs.size(0)
+            x = TF.time_to_batch(hs)                           # [B*T,C,h,w]  (stack+permute+merge_frames)
 
         abstract, rendered = [], []
         for i in range(len(self.render_blocks)):

@@ -43,7 +43,7 @@ def alias_reference_modules():
     `{'optim': optimizer, 'txt': seq2seq}`) resolve their `txt2vid.*` class paths to this package's drop-in classes."""
     import sys
     for ours in ('', '.models', '.models.txt', '.models.txt.basic', '.models.layers', '.models.conv_lstm', '.models.resnet3d',
-                 '.models.tganv2', '.models.tganv2.gen', '.models.tganv2.discrim', '.models.tganv2_cond', '.models.tganv2_cond.gen',
+                 '.models.tgan', '.models.tgan.temporal_gen', '.models.tganv2', '.models.tganv2.gen', '.models.tganv2.discrim', '.models.tganv2_cond', '.models.tganv2_cond.gen',
                  '.models.tganv2_cond.discrim', '.gan', '.gan.losses', '.gan.cond_gan', '.data', '.util', '.util.pick'):
         theirs = 'txt2vid' + ours
         if theirs not in sys.modules:
