@@ -42,8 +42,10 @@ class HostDraws(object):
 
 
 class StaticDraws(object):
-    def __init__(self, device, batch, latent, n_levels, n_gen_phases=3, gp=True, subsample_input=True, n_perms=0):
-        self.n_perms = n_perms                      # caption permutations per iteration (conditional path: D step, G step)
+    def __init__(self, device, batch, latent, n_levels, n_gen_phases=3, gp=True, subsample_input=True, n_perms=0,
+                 n_d_steps=1, n_g_steps=1):
+        self.n_perms = n_perms                      # caption permutations per iteration (conditional path: D steps, real_pred)
+        self.n_d_steps, self.n_g_steps = n_d_steps, n_g_steps     # one set of GP alphas per D step, of G phases per G forward
         self._p = 0
         self.device, self.batch, self.latent = device, batch, latent
         self.n_levels, self.n_gen, self.gp, self.sub = n_levels, n_gen_phases, gp, subsample_input
@@ -53,16 +55,19 @@ class StaticDraws(object):
         # one pinned staging buffer and one device buffer of 32-bit words for every draw of an iteration (int32 phases |
         # float32 z | float32 alphas | int32 caption permutations): ONE H2D copy node per replayed iteration instead of four
         # (a copy node costs ~20 us of idle time in the replayed graph)
-        n_int, n_z, n_a, n_p = n_levels + n_gen_phases, batch * latent, sum(self.bs), max(1, n_perms) * batch
+        n_int, n_z, n_a, n_p = n_levels + n_gen_phases * n_g_steps, batch * latent, sum(self.bs) * n_d_steps, max(1, n_perms) * batch
         # The staging side is a RING of pinned buffers: the upload is asynchronous and the training loop runs the host ahead of
         # the GPU (losses are read one iteration late), so a single staging buffer would be rewritten with iteration i + 1's draws
         # before the copy of iteration i has executed. A slot is reused only after the event behind its last copy has completed.
         self.RING = 4
-        self.h_ring = [torch.zeros(n_int + n_z + n_a + n_p, dtype=torch.int32).pin_memory() for _ in range(self.RING)]
+        on_gpu = torch.device(device).type != 'cpu'        # (a CPU "device": the host-side draw order alone, no pinned memory)
+        self.h_ring = [torch.zeros(n_int + n_z + n_a + n_p, dtype=torch.int32) for _ in range(self.RING)]
+        if on_gpu:
+            self.h_ring = [h.pin_memory() for h in self.h_ring]
         self.h_events = [None] * self.RING
         self._slot = 0
         self.h_all = self.h_ring[0]
-        self.d_all = self.h_all.to(device)               # (zeros by copy: a memcpy, no fill kernel)
+        self.d_all = self.h_all.to(device) if on_gpu else self.h_all.clone()     # (zeros by copy: a memcpy, no fill kernel)
 
         def carve(buf):
             o = 0
@@ -77,8 +82,10 @@ class StaticDraws(object):
         self._i = self._a = 0
 
     def begin_step(self):
-        """All host draws of one iteration, reference order: n_levels Subsample phases, z, the generator's
-        phases, the GP alphas per level; then one small H2D copy on the current stream."""
+        """All host draws of one iteration, reference order (trainer.py:221-263): n_levels Subsample phases, z, the generator's
+        phases of its first forward, the GP alphas per level of every D step, the generator's phases of every later G
+        forward; numpy: the caption permutations in the order they are consumed. Then one small H2D copy on the current
+        stream."""
         slot = self._slot
         self._slot = (slot + 1) % self.RING
         if self.h_events[slot] is not None:
@@ -96,9 +103,12 @@ class StaticDraws(object):
             self.h_int[self.n_levels + k] = int(torch.randint(2, (1,)))
         if self.gp:
             off = 0
-            for b in self.bs:
-                self.h_a[off:off + b] = torch.rand(b, 1, 1, 1, 1).reshape(b)
-                off += b
+            for _ in range(self.n_d_steps):
+                for b in self.bs:
+                    self.h_a[off:off + b] = torch.rand(b, 1, 1, 1, 1).reshape(b)
+                    off += b
+        for k in range(self.n_gen, self.n_gen * self.n_g_steps):
+            self.h_int[self.n_levels + k] = int(torch.randint(2, (1,)))
         if self.n_perms:
             from .util.misc import gen_perm
             for k in range(self.n_perms):

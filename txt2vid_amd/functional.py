@@ -2161,6 +2161,13 @@ def ones_like(t):
     return out
 
 
+def full_scalar(value, device):
+    """A 0-d float32 device tensor holding `value` (one fill launch)."""
+    out = torch.empty((), device=device, dtype=torch.float32)
+    check(lib().t2v_fill(_p(out), float(value), 1, _stream()), 't2v_fill')
+    return out
+
+
 _ones = {}
 
 

@@ -149,14 +149,15 @@ class CondGan(object):
             l = TF.scalar_sum([l, gp], weights=[1.0, gp_lambda])
         return l, fake_pred, real_pred
 
-    def gen_step_fused(self, fake=None, real=None, cond=None, loss=None):
+    def gen_step_fused(self, fake=None, real=None, cond=None, loss=None, draw_perm=True):
         """`all_discrim_forward(real)` + `gen_step(fake, real_pred)` (trainer.py:247-263) as ONE lock-step pass
         of the frozen, freshly updated D over the generated AND the (detached) real clips: identical values,
-        half the launches; the backward only runs through the generated half."""
+        half the launches; the backward only runs through the generated half. `draw_perm=False`: a later G step of
+        the same iteration, whose real_pred the reference does not recompute (no permutation is drawn)."""
         self.gen.zero_grad()
         if self.cond_encoder is not None:
             self.cond_encoder.zero_grad()
-        if cond is not None:
+        if cond is not None and draw_perm:
             TF.draws.perm(cond[0].size(0), cond[0].device)        # the reference's all_discrim_forward draws a permutation here
         losses = []
         n = len(fake)

@@ -4,7 +4,9 @@ bench.py and the parity tests drive exactly what `train()` runs.
 
 Random draws follow the reference order on the HOST generators (SURVEY §7 "RNG parity"): 4x Subsample
 phase (trainer.py:157-158), z (trainer.py:221, drawn on the CPU and copied), 3x Subsample in G,
-gen_perm (numpy), 4x GP alpha (losses.py:140-145), gen_perm for real_pred (trainer.py:247).
+gen_perm (numpy), 4x GP alpha (losses.py:140-145), gen_perm for real_pred (trainer.py:247). Under the
+--discrim_steps N / --gen_steps M schedule (trainer.py:228-263): gen_perm + 4x alpha once per D step, then
+gen_perm for real_pred, then 3x Subsample per later G forward (DESIGN "D:G step schedule").
 """
 import os
 import sys
@@ -80,18 +82,35 @@ def multiscale_data(x, cond, frame_sizes, subsample_input=True):
 
 
 class TrainStep(object):
-    """The loop body trainer.py:199-267 after data loading, cut at the two points where data-parallel
-    ranks exchange gradients:  part_d (pyramid, G forward, D loss + GP, D backward)  |sync D grads|
-    part_g (Adam on D, real_pred, G loss, G backward)  |sync G grads|  part_end (Adam on G).
-    Eager mode runs the three parts back to back; `GraphedTrainStep` captures each part as a HIP graph."""
+    """The loop body trainer.py:199-267 after data loading, for the schedule of N = --discrim_steps D steps and
+    M = --gen_steps G steps, cut after every backward pass (where data-parallel ranks exchange gradients):
+      D part 0   pyramid, G forward, D loss + GP, D backward                     |sync D grads|
+      D part j   Adam on D, D loss + GP, D backward                  (1 <= j < N) |sync D grads|
+      G part 0   Adam on D, real_pred / fused G loss, G backward                  |sync G grads|
+      G part j   Adam on G, G re-forward (same z), G loss, G backward (1 <= j < M) |sync G grads|
+      end        Adam on G.
+    N = M = 1 is the three parts part_d | part_g | part_end. Eager mode runs the parts back to back;
+    `GraphedTrainStep` captures them as HIP graphs."""
 
     def __init__(self, gan, optD, optG, losses, params, device, end2end=False, grad_sync=None):
-        if params.discrim_steps != 1 or params.gen_steps != 1:
-            raise NotImplementedError('the canonical 1 D step : 1 G step schedule (scripts/run_tganv2*.sh) is built')
+        self.n_d, self.n_g = int(params.discrim_steps), int(params.gen_steps)
+        if self.n_d < 1 or self.n_g < 1:
+            raise ValueError('--discrim_steps and --gen_steps must be >= 1 (got %d and %d)' % (self.n_d, self.n_g))
         self.gan, self.optD, self.optG, self.losses, self.params = gan, optD, optG, losses, params
         self.device, self.end2end, self.grad_sync = device, end2end, grad_sync
         self.lD = self.lG = self.fake = self.xs = self.conds = None
+        self._z = self._real_pred = None
+        self._fused = False
         self._one = None                  # dL/dL = 1 for both backward passes: one persistent 0-d tensor (no fill launch per pass)
+        # the store_false quirk of --no_mean_*_loss (trainer.py:236-237,260-261): the loss of every step is divided by the step
+        # count only when the flag was PASSED (its value is then False)
+        self.d_scale = 1.0 if getattr(params, 'no_mean_discrim_loss', True) else 1.0 / self.n_d
+        self.g_scale = 1.0 if getattr(params, 'no_mean_gen_loss', True) else 1.0 / self.n_g
+        # the backward roots 1/N, 1/M: filled here, outside any graph capture, and never written again
+        self._scaled = {}
+        if torch.device(device).type == 'cuda':
+            for s in {self.d_scale, self.g_scale} - {1.0}:
+                self._scaled[s] = TF.full_scalar(s, device)
         # weight / bias gradients land directly in flat per-model arenas (the ones the data-parallel exchange
         # all-reduces, when there is one): no per-parameter sums, no gather copies
         self.grad_sink = None
@@ -105,7 +124,9 @@ class TrainStep(object):
                 gan.__dict__['_t2v_grad_sink'] = cached          # one pair of arenas per model, reused by every step
             self.grad_sink = cached[1]
 
-    def _root(self, loss):
+    def _root(self, loss, scale=1.0):
+        if scale != 1.0:
+            return self._scaled[scale].view(loss.shape)
         if self._one is None or self._one.device != loss.device or self._one.shape != loss.shape:
             self._one = TF.ones_like(loss.detach())
         return self._one
@@ -114,25 +135,51 @@ class TrainStep(object):
         TF.set_grad_sink(self.grad_sink)
         TF.grad_sink_reset()              # the step about to run clears this model's gradients first
 
-    def part_d(self, x, cond):
+    @staticmethod
+    def _total(total, loss, scale):
+        """total + scale * loss on the device (the reference's `total_*_loss += float(loss)`, without a host sync)."""
+        loss = loss.detach()
+        if total is None:
+            return loss if scale == 1.0 else TF.scalar_sum([loss], weights=[scale])
+        return TF.scalar_sum([total, loss], weights=[1.0, scale])
+
+    def _forward_g(self):
+        return self.gan(self._z, cond=self.conds[0] if self.conds is not None else None)
+
+    def _d_step(self, arm=True):
         p = self.params
-        self._arm_sink()
-        self.xs, self.conds = multiscale_data(x, cond, p.frame_sizes, p.subsample_input)
-        z = TF.draws.z(x.size(0), self.gan.gen.latent_size, self.device)       # CPU generator, then copy (parity)
-        self.fake = self.gan(z, cond=self.conds[0] if self.conds is not None else None)
+        if arm:
+            self._arm_sink()
         loss = self.gan.discrim_step(real=self.xs, fake=[f.detach() for f in self.fake], cond=self.conds,
                                      loss=self.losses.discrim_loss, gp_lambda=p.gp_lambda)
-        loss.backward(gradient=self._root(loss), retain_graph=self.end2end)
+        loss.backward(gradient=self._root(loss, self.d_scale), retain_graph=self.end2end)
         TF.grad_sink_flush()              # the weight-gradient partial sums of the whole pass, summed in one launch
-        self.lD = loss.detach()
+        self.lD = self._total(self.lD, loss, self.d_scale)
+
+    def part_d(self, x, cond):
+        """D part 0: pyramid, z, G forward and the first D step."""
+        p = self.params
+        self.lD = self.lG = self._real_pred = None
+        self._arm_sink()
+        self.xs, self.conds = multiscale_data(x, cond, p.frame_sizes, p.subsample_input)
+        self._z = TF.draws.z(x.size(0), self.gan.gen.latent_size, self.device)       # CPU generator, then copy (parity)
+        self.fake = self._forward_g()
+        self._d_step(arm=False)
+
+    def part_d_more(self):
+        """D part j >= 1: D's update from step j - 1, then D step j against the same pyramid and the same generated clips."""
+        self.optD.step()
+        self._d_step()
 
     def part_g(self):
+        """G part 0: D's last update, real_pred (ONE pass per iteration, trainer.py:247) and the first G step."""
         self.optD.step()
         self._arm_sink()
         # D after its update, on the real batch (trainer.py:247). Its graph is only needed when the text
         # encoder trains end-to-end; otherwise nothing upstream of these predictions receives a gradient
         # that is ever used, so none is recorded (identical results, SURVEY §7 "wasted work").
-        if not self.end2end and self.gan.can_fuse_gen_step(self.fake, self.xs):
+        self._fused = not self.end2end and self.gan.can_fuse_gen_step(self.fake, self.xs)
+        if self._fused:
             loss = self.gan.gen_step_fused(fake=self.fake, real=self.xs, cond=self.conds, loss=self.losses.gen_loss)
         else:
             if self.end2end:
@@ -140,22 +187,62 @@ class TrainStep(object):
             else:
                 with torch.no_grad():
                     _, _, real_pred = self.gan.all_discrim_forward(real=self.xs, cond=self.conds, fake=None, loss=None)
+            if self.n_g > 1:
+                self._real_pred = real_pred
             loss = self.gan.gen_step(fake=self.fake, real_pred=real_pred, cond=self.conds, loss=self.losses.gen_loss)
-        loss.backward(gradient=self._root(loss))
+        self._g_backward(loss, last=self.n_g == 1)
+
+    def part_g_more(self, last):
+        """G part j >= 1: G's update from step j - 1, a new train-mode G forward of the same z (new Subsample phases, BatchNorm
+        buffers updated again) and G step j against the same real_pred. D is unchanged since G part 0, so the fused pass
+        recomputes the same real_pred; it draws no caption permutation (the reference draws that one once, trainer.py:247)."""
+        self.optG.step()
+        self._arm_sink()
+        self.fake = self._forward_g()
+        if self._fused:
+            loss = self.gan.gen_step_fused(fake=self.fake, real=self.xs, cond=self.conds, loss=self.losses.gen_loss,
+                                           draw_perm=False)
+        else:
+            loss = self.gan.gen_step(fake=self.fake, real_pred=self._real_pred, cond=self.conds, loss=self.losses.gen_loss)
+        self._g_backward(loss, last)
+
+    def _g_backward(self, loss, last):
+        # --end2end: real_pred and the sentence code keep their graphs for the next G step (trainer.py:262)
+        loss.backward(gradient=self._root(loss, self.g_scale), retain_graph=self.end2end and not last)
         TF.grad_sink_flush()
-        self.lG = loss.detach()
+        self.lG = self._total(self.lG, loss, self.g_scale)
+        if last:
+            self._real_pred = None
 
     def part_end(self):
         self.optG.step()
 
+    @property
+    def n_parts(self):
+        return self.n_d + self.n_g + 1
+
+    def part(self, k, x=None, cond=None):
+        """Run part k of `n_parts`. Returns which model's gradients the data-parallel ranks exchange after it ('D', 'G', or None
+        after the last part)."""
+        N, M = self.n_d, self.n_g
+        if k == 0:
+            self.part_d(x, cond)
+        elif k < N:
+            self.part_d_more()
+        elif k == N:
+            self.part_g()
+        elif k < N + M:
+            self.part_g_more(last=k == N + M - 1)
+        else:
+            self.part_end()
+            return None
+        return 'D' if k < N else 'G'
+
     def run(self, x, cond=None):
-        self.part_d(x, cond)
-        if self.grad_sync is not None:
-            self.grad_sync('D')
-        self.part_g()
-        if self.grad_sync is not None:
-            self.grad_sync('G')
-        self.part_end()
+        for k in range(self.n_parts):
+            which = self.part(k, x, cond)
+            if which is not None and self.grad_sync is not None:
+                self.grad_sync(which)
         return self.lD, self.lG, self.fake, self.xs
 
 
@@ -170,9 +257,9 @@ _DRAWS_LAST = os.environ.get('T2V_DRAWS_LAST') is not None
 
 
 class GraphedTrainStep(object):
-    """HIP-graph replay of the training iteration (unconditional path): after `warmup` eager iterations
-    the three parts of `TrainStep` are captured once (shared memory pool) and every later iteration is
-    3 graph launches + the eager gradient exchange between them (one process: ONE graph for the whole iteration). All per-iteration randomness is drawn
+    """HIP-graph replay of the training iteration: after `warmup` eager iterations the N + M + 1 parts of `TrainStep`
+    are captured once (shared memory pool) and every later iteration is N + M + 1 graph launches + the N + M eager
+    gradient exchanges between them (one process: ONE graph for the whole iteration). All per-iteration randomness is drawn
     on the host in the reference's order and uploaded into fixed buffers before the replay
     (`functional.StaticDraws`); the batch is copied into a fixed input buffer."""
 
@@ -180,14 +267,16 @@ class GraphedTrainStep(object):
         self.ts = TrainStep(gan, optD, optG, losses, params, device, False, grad_sync)
         self.device, self.grad_sync, self.warmup = device, grad_sync, warmup
         n_levels = len(params.frame_sizes)
+        N, M = self.ts.n_d, self.ts.n_g
         self.draws = TF.StaticDraws(device, batch_shape[0], gan.gen.latent_size, n_levels, n_gen_phases=n_levels - 1,
                                     gp=params.gp_lambda > 0, subsample_input=params.subsample_input,
-                                    n_perms=2 * len(gan.discrims) if cond_dim else 0)
+                                    n_perms=(N + 1) * len(gan.discrims) if cond_dim else 0, n_d_steps=N, n_g_steps=M)
         self.x = torch.empty(batch_shape, device=device, dtype=torch.float32)
         # conditional path: the sentence code is computed outside the graphs (its sequence length varies) into a fixed buffer
         self.cond = torch.empty((batch_shape[0], cond_dim), device=device, dtype=torch.float32) if cond_dim else None
         self.graphs = None
-        self.n_graphs = 0                    # graphs per iteration of the last capture (1 without a gradient exchange, else 3)
+        self.n_graphs = 0                    # graphs per iteration of the last capture (1 without a gradient exchange, else N + M + 1)
+        self.exchanges = ()                  # the gradient exchanges between them ('D' x N, 'G' x M)
         self.n = 0
         # warm-up and capture run on ONE side stream (the autograd graph's AccumulateGrad nodes remember
         # the stream they were created on; capture must see the same one)
@@ -200,45 +289,45 @@ class GraphedTrainStep(object):
         for opt in (self.ts.optD, self.ts.optG):
             opt.make_capturable(self.device)
         # drop every reference into the previous iteration's autograd graph before capturing
-        self.ts.lD = self.ts.lG = self.ts.fake = self.ts.xs = self.ts.conds = None
+        self.ts.lD = self.ts.lG = self.ts.fake = self.ts.xs = self.ts.conds = self.ts._real_pred = None
         torch.cuda.synchronize()
-        g1, g2, g3 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         self.draws.rewind()
         gs = self.grad_sync
         # thread-local capture mode: the data loader's pin-memory thread keeps issuing pinned allocations and H2D copies
         # while this thread captures; in the default (global) mode any such call invalidates the capture
         mode = 'thread_local'
+        n_parts = self.ts.n_parts
         if gs is None and os.environ.get('T2V_THREE_GRAPHS') is None:      # (T2V_THREE_GRAPHS: developer A/B switch)
-            # one process, no gradient exchange between the parts: the whole iteration is ONE graph (two replay launches fewer)
+            # one process, no gradient exchange between the parts: the whole iteration is ONE graph (fewer replay launches)
+            g1 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g1, stream=self.side, capture_error_mode=mode):
-                self.ts.part_d(self.x, self.cond)
-                self.ts.part_g()
-                self.ts.part_end()
+                for k in range(n_parts):
+                    self.ts.part(k, self.x, self.cond)
             torch.cuda.synchronize()
             self.graphs = (g1,)
             self.n_graphs = 1
+            self.exchanges = ()
             if self.ts.grad_sink is not None:
                 self.ts.grad_sink.frozen += 1
             return
-        with torch.cuda.graph(g1, stream=self.side, capture_error_mode=mode):
-            self.ts.part_d(self.x, self.cond)
-            if gs is not None:
-                gs.pre('D')                 # p.grad -> arena: captured (the replayed backward rewrites the same buffers)
-        if gs is not None:
-            gs.exchange('D')
-            gs.post('D')                    # Adam (captured next) reads the arena views
-        with torch.cuda.graph(g2, pool=g1.pool(), stream=self.side, capture_error_mode=mode):
-            self.ts.part_g()
-            if gs is not None:
-                gs.pre('G')
-        if gs is not None:
-            gs.exchange('G')
-            gs.post('G')
-        with torch.cuda.graph(g3, pool=g1.pool(), stream=self.side, capture_error_mode=mode):
-            self.ts.part_end()
+        # one graph per part (shared memory pool); the exchange of the gradients the part computed sits after it
+        graphs, exchanges = [], []
+        for k in range(n_parts):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None, stream=self.side, capture_error_mode=mode):
+                which = self.ts.part(k, self.x, self.cond)
+                if gs is not None and which is not None:
+                    gs.pre(which)           # p.grad -> arena: captured (the replayed backward rewrites the same buffers)
+            graphs.append(g)
+            if which is not None:
+                exchanges.append(which)
+                if gs is not None:
+                    gs.exchange(which)
+                    gs.post(which)          # Adam (captured next) reads the arena views
         torch.cuda.synchronize()
-        self.graphs = (g1, g2, g3)
-        self.n_graphs = 3
+        self.graphs = tuple(graphs)
+        self.n_graphs = len(graphs)
+        self.exchanges = tuple(exchanges)
         if self.ts.grad_sink is not None:
             self.ts.grad_sink.frozen += 1        # the graphs bake in the sink's slab addresses and table slots
 
@@ -282,13 +371,11 @@ class GraphedTrainStep(object):
                 cur.wait_stream(self.side)
             else:
                 self.graphs[0].replay()
-                if len(self.graphs) == 3:                 # data-parallel: the two exchanges sit between the captured parts
+                # data-parallel: the N + M exchanges sit between the N + M + 1 captured parts
+                for which, g in zip(self.exchanges, self.graphs[1:]):
                     if self.grad_sync is not None:
-                        self.grad_sync.exchange('D')
-                    self.graphs[1].replay()
-                    if self.grad_sync is not None:
-                        self.grad_sync.exchange('G')
-                    self.graphs[2].replay()
+                        self.grad_sync.exchange(which)
+                    g.replay()
             self.n += 1
         finally:
             TF.set_draws(old)
@@ -394,7 +481,7 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
     from ..dist import rank_world
     writer = rank_world()[0] == 0            # data-parallel replicas are identical: rank 0 alone writes checkpoints and samples
     iteration = 0
-    # HIP-graph replay of the iteration (3 graphs, see GraphedTrainStep) unless --no_graph / --end2end: the eager loop is
+    # HIP-graph replay of the iteration (see GraphedTrainStep) unless --no_graph / --end2end: the eager loop is
     # host-bound (~1 000 launches at ~20 us of Python each)
     use_graph = not end2end and not getattr(params, 'no_graph', False) and torch.device(device).type == 'cuda'
     graphed, graphed_key, pending, loss_ring, graphed_encoder = None, None, None, None, None
