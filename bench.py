@@ -11,6 +11,10 @@ backward, Adam, real_pred, G loss backward through D, Adam). Prints ONE JSON lin
 
     --dump-outputs DIR   after the timed steps, rank 0 writes what the last of them computed as DIR/<name>.npy (see
                          dump_outputs); models, batches and random draws are seeded, so equal arguments give equal inputs
+    --full               also the side measurements after the headline (each --no_* option drops one of them): the roofline
+                         passes (an instrumented eager pass, D forward+backward), eval-mode sampling, the CLI loop, the CPU
+                         baseline, the HBM-bound kernels and the extra BASELINE configs[2] / configs[3] records (child jobs).
+                         Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line.
 """
 import argparse
 import ctypes as C
@@ -151,14 +155,15 @@ def child_env():
 
 
 def extra_record(flags, timeout=600, roofline=False):
-    """Run `python bench.py <flags>` as a child JOB (no CPU baseline, no roofline passes; with `--gpus N` it starts its own N ranks)
-    and return the fields of its JSON line that identify and size the measurement; an error string if it failed or timed out.
+    """Run `python bench.py <flags>` as a child JOB (a plain run; with `roofline`, a `--full` one whose only side measurement is
+    the roofline object; with `--gpus N` it starts its own N ranks) and return the fields of its JSON line that identify and
+    size the measurement; an error string if it failed or timed out.
     A child job cannot take this process's headline down: a rank that raises or hangs in there only loses the extra record
     (the child's whole process group is killed at the timeout)."""
     import signal
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__)] + flags + ['--no_cpu_baseline', '--no_d_roofline', '--no_extra', '--no_hbm'] + \
-        ([] if roofline else ['--no_roofline'])
+    cmd = [sys.executable, os.path.abspath(__file__)] + flags + \
+        (['--full', '--no_cpu_baseline', '--no_d_roofline', '--no_extra', '--no_hbm'] if roofline else [])
     try:
         p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=child_env(), start_new_session=True)
         try:
@@ -446,9 +451,12 @@ def main():
                                                                           '= the per-GPU share of BASELINE configs[4] (MSRVDC shape)')
     ap.add_argument('--channels', type=int, default=1, choices=(1, 3))
     ap.add_argument('--no_hbm', action='store_true', help='skip the HBM-bound kernels block')
-    ap.add_argument('--no_extra', action='store_true', help='skip the extra BASELINE configs[2] record (text-conditioned, bf16 compute) of the default run')
+    ap.add_argument('--no_extra', action='store_true', help='skip the extra BASELINE configs[2] / configs[3] record (text-conditioned, bf16 compute) of a --full run')
     ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (losses, generated '
                                                           'videos, a seeded sample of the updated weights; at most 64 MB)')
+    ap.add_argument('--full', action='store_true', help='also run the side measurements after the headline (roofline passes, sampling, '
+                                                        'CLI loop, CPU baseline, HBM-bound kernels, extra configs records); '
+                                                        'the --no_* options drop single ones of them')
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
@@ -483,7 +491,7 @@ def main():
             sys.stderr.write('[bench %.1fs] %s\n' % (time.perf_counter() - T0, msg))
             sys.stderr.flush()
 
-    prof = not args.no_roofline
+    prof = args.full and not args.no_roofline
     R = timed_run(args, args.cond, args.size, args.channels, args.steps, args.warmup, rank, world, dev, log, prof_eager=prof)
     args.warmup = R.warmup
     gan, optD, optG, losses, prm, pool, graphed, grad_sync, txt = R.gan, R.optD, R.optG, R.losses, R.prm, R.pool, R.graphed, R.grad_sync, R.txt
@@ -622,7 +630,7 @@ def main():
             res['d_fwdbwd_roofline'] = d_fwdbwd_roofline(batch=args.batch, iters=3, device=dev)
         except Exception as e:                                    # side measurements never take the headline down
             res['d_fwdbwd_roofline'] = {'error': repr(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_extra and not args.cond and not bf16 and default_shape:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and not args.cond and not bf16 and default_shape:
         log('sampling (eval-mode generator) and the CLI loop')
         try:
             res['sampling'] = sampling_record(gan, args.batch, dev)
@@ -633,13 +641,13 @@ def main():
                 res['cli_ms_per_iter'] = cli_record(args.batch)
             except Exception as e:
                 res['cli_ms_per_iter'] = {'error': repr(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.cond and default_shape:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.cond and default_shape:
         log('timing the CPU oracle on %d host threads' % host_threads())
         try:
             res['cpu_baseline'] = cpu_baseline(host_threads())
         except Exception as e:
             res['cpu_baseline'] = {'error': repr(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_extra and not args.cond and not bf16 and default_shape and not args.eager:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and not args.cond and not bf16 and default_shape and not args.eager:
         # BASELINE configs[2] (text-conditioned, Bi-LSTM sentence codes, non-local blocks on, bf16 compute) as an EXTRA record of the
         # same line: measured by a child process after this one's timed region, never part of `value`
         log('extra record: BASELINE configs[2] (child process)')
@@ -661,7 +669,7 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()     # the headline is complete: nothing below takes part in a collective of THIS job
-    if world > 1 and rank == 0 and not args.no_extra and not args.cond and not bf16 and default_shape and not args.eager:
+    if world > 1 and rank == 0 and args.full and not args.no_extra and not args.cond and not bf16 and default_shape and not args.eager:
         # BASELINE configs[3] (the scaling config: text-conditioned, bf16 compute, per-GPU batch 32, RCCL data parallel) as an EXTRA
         # record beside the configs[1] value — never part of `value`. It runs as a CHILD JOB with its own ranks (the other ranks of
         # this job have left by now): a rank of it that raises or hangs costs the extra record, never the headline line below.

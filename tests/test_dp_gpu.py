@@ -51,7 +51,7 @@ def test_bench_starts_its_own_ranks():
         env.update(T2V_DIST_BACKEND='gloo', T2V_SINGLE_DEVICE='1')
     env.pop('WORLD_SIZE', None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '3', '--batch', '8',
-           '--no_cpu_baseline', '--no_roofline']
+           '--full', '--no_cpu_baseline', '--no_roofline']
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors='replace')[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
@@ -62,7 +62,7 @@ def test_bench_starts_its_own_ranks():
     # the two per-step collectives are event-timed inside the timed region; `rccl_ranks` says whether they ran over RCCL
     assert res['allreduce_ms_per_step'] > 0 and res['allreduce']['collectives_per_step'] >= 2
     assert res['rccl_ranks'] == (2 if torch.cuda.device_count() >= 2 else 0)
-    # BASELINE's scaling config (configs[3]: text-conditioned, bf16 compute) rides along as an extra record on the same ranks
+    # with --full, BASELINE's scaling config (configs[3]: text-conditioned, bf16 compute) rides along as an extra record on the same ranks
     c3 = res['extra_records']['configs[3]']
     assert 'error' not in c3, c3
     assert c3['n_gpus'] == 2 and c3['value'] > 0 and c3['allreduce_ms_per_step'] > 0 and np.isfinite(c3['final_losses']['lossD'])

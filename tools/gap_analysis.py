@@ -1,7 +1,7 @@
 """Timeline of the graph-replayed steps from a rocprofv3 --kernel-trace CSV: GPU-busy time, idle gaps, and which
 kernels the gaps follow. Usage: python tools/gap_analysis.py <rocprof dir> <ms_per_step> [n_steps_to_analyse]
 
-[auto | start fraction]. The bench's eager warm-ups run before the timed region and its instrumented pass after it, so the
+[auto | start fraction]. The bench's eager warm-ups run before the timed region and (--full) its instrumented pass after it, so the
 window of n steps is placed on the densest stretch of the trace (the graph replays) unless a start fraction is given."""
 import collections
 import csv

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 O=$R/gpurun_out/r03
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_d_roofline --no_extra > $O/trace.log 2>&1 && echo "trace ok"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_d_roofline --no_extra > $O/trace.log 2>&1 && echo "trace ok"
 rc=$?
 cp $O/trace/*/*_kernel_stats.csv $O/r03_kernel_stats.csv 2>/dev/null
 python3 $R/tools/prof_summary.py $O/trace > $O/r03_kernel_trace_summary.txt 2>&1
@@ -25,7 +25,7 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_hbm_writ
 python3 tools/pmc_hbm.py $O/pmc_hbm_fetch $O/pmc_hbm_write > $O/r03_pmc_hbm.json && echo "hbm pmc ok"
 cp $O/r03_pmc_hbm.json profiles/r03_pmc_hbm.json
 # per-launch shape table of one iteration's convolution launches (T2V_PROF_DUMP) + the default line
-T2V_PROF_DUMP=$O/r03_conv_launches.csv python3 bench.py > $O/bench_default.log 2>&1 && tail -1 $O/bench_default.log > $O/r03_bench_default.json && echo "bench ok"
+T2V_PROF_DUMP=$O/r03_conv_launches.csv python3 bench.py --full > $O/bench_default.log 2>&1 && tail -1 $O/bench_default.log > $O/r03_bench_default.json && echo "bench ok"
 python3 tools/launch_table.py $O/r03_conv_launches.csv 5 > $O/r03_conv_launch_shapes.txt 2>&1
 # D forward+backward (the north star's own line) and BASELINE configs[2] under the profiler
 cd /tmp
