@@ -585,6 +585,16 @@ int t2v_tseed_fwd_tanh(const float* x, const float* ss_in, const float* w, const
 int t2v_tseed_bwd(const float* g, const float* z, const float* w, const float* a_in, const float* st_in, float* gin, float* dw,
                   float* db, float* dgamma, float* dbeta, int B, int Cin, int Cout, int Lin, int K, int flags, void* stream);
 
+/* ---- conditioning augmentation of the text-conditioned generator (StackGAN++ CA; opt-in, MultiScaleGen(ca_dim=D)) ------------
+ * h [B, 4D] = CA's fc of the sentence code. GLU: mu = h[:, :D] * sigmoid(h[:, 2D:3D]), logvar = h[:, D:2D] * sigmoid(h[:, 3D:]).
+ * t2v_ca_fwd: out [B, L + D] = [z | mu + eps * exp(logvar / 2)] (z [B, L], eps [B, D]), the generator's whole fc input row;
+ *   kl[0] = mean over B*D of -0.5 * (1 + logvar - mu^2 - exp(logvar)). One workgroup, fixed-order reduction (deterministic).
+ * t2v_ca_bwd: gh [B, 4D] = dL/dh from gout = dL/dout [B, L + D] (only its last D columns are read; may be null) and
+ *   kl_coeff * gkl[0] (gkl a device scalar dL/dKL; may be null). fp32 only. */
+int t2v_ca_fwd(const float* h, const float* z, const float* eps, float* out, float* kl, int B, int L, int D, void* stream);
+int t2v_ca_bwd(const float* gout, const float* gkl, float kl_coeff, const float* h, const float* eps, float* gh, int B, int L, int D,
+               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

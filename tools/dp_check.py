@@ -3,9 +3,11 @@ the graph-replayed iteration with the gradient sink + the per-step arena all-red
 same weights, and those must differ from what a rank would have learnt alone (the exchange is live).
 
     T2V_DIST_BACKEND=gloo T2V_SINGLE_DEVICE=1 python -m torch.distributed.run --nproc-per-node 2 \\
-        --master-addr 127.0.0.1 --master-port 29531 tools/dp_check.py [--discrim_steps N] [--gen_steps M]
+        --master-addr 127.0.0.1 --master-port 29531 tools/dp_check.py [--discrim_steps N] [--gen_steps M] [--cond [--ca_dim D]]
 
 With a schedule other than 1:1 the line also reports the graphs and the exchanges ('D' / 'G') of one replayed iteration.
+--cond: the text-conditioned models (a randomly initialised Bi-LSTM sentence encoder, 8-token captions per rank); --ca_dim D > 0
+puts the generator's conditioning augmentation in front of its fc (built here: bench.build_models has no such argument).
 """
 import argparse
 import os
@@ -29,7 +31,11 @@ B = 4
 ap = argparse.ArgumentParser()
 ap.add_argument('--discrim_steps', type=int, default=1)
 ap.add_argument('--gen_steps', type=int, default=1)
+ap.add_argument('--cond', action='store_true')
+ap.add_argument('--ca_dim', type=int, default=0)
 args = ap.parse_args()
+if args.ca_dim and not args.cond:
+    ap.error('--ca_dim needs --cond')
 
 
 class Params(bench.Params):
@@ -37,9 +43,39 @@ class Params(bench.Params):
     gen_steps = args.gen_steps
 
 
+def build_cond(seed=100):
+    """bench.build_models(cond=True) with the generator's conditioning augmentation, plus the sentence encoder."""
+    from txt2vid_amd.models.tganv2_cond.gen import MultiScaleGen
+    from txt2vid_amd.models.tganv2_cond.discrim import MultiScaleDiscrim
+    from txt2vid_amd.models.txt.basic import Seq2Seq
+    from txt2vid_amd.data import Vocab
+    from txt2vid_amd.gan.cond_gan import CondGan
+    from txt2vid_amd.gan.losses import MixedGanLoss, RSGANLoss
+    from txt2vid_amd.optim import Adam
+    from txt2vid_amd.util.torch.init import init
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    gen = MultiScaleGen(width=64, height=64, num_channels=1, cond_dim=256, ca_dim=args.ca_dim)
+    dis = MultiScaleDiscrim(num_channels=1, cond_dim=256)
+    txt = Seq2Seq(vocab_size=len(Vocab()))
+    for m in (gen, dis, txt):
+        init(m, 'xavier')
+        m.to(dev)
+    gen.train()
+    dis.train()
+    optD = Adam([{'params': dis.parameters()}], lr=2e-4, betas=(0.5, 0.999))
+    optG = Adam([{'params': gen.parameters()}], lr=2e-4, betas=(0.5, 0.999))
+    return gen, dis, optD, optG, MixedGanLoss(g_loss=RSGANLoss(), d_loss=RSGANLoss()), CondGan, txt
+
+
 def run(sync):
-    gen, dis, optD, optG, losses, CondGan = bench.build_models(dev)             # same seed -> identical replicas
-    gan = CondGan(gen=gen, discrims=[dis], discrim_names=['video'], gp_scale=float(world if sync else 1))
+    txt = None
+    if args.cond:
+        gen, dis, optD, optG, losses, CondGan, txt = build_cond()
+    else:
+        gen, dis, optD, optG, losses, CondGan = bench.build_models(dev)         # same seed -> identical replicas
+    gan = CondGan(gen=gen, discrims=[dis], cond_encoder=txt, discrim_names=['video'], gp_scale=float(world if sync else 1))
     gs = None
     if sync:
         arenas = {'D': tdist.model_arena(dis, TF.copy_into), 'G': tdist.model_arena(gen, TF.copy_into)}
@@ -48,7 +84,15 @@ def run(sync):
     random.seed(100 + rank)
     np.random.seed(100 + rank)
     torch.manual_seed(100 + rank)
-    step = GraphedTrainStep(gan, optD, optG, losses, Params(), dev, tuple(pool[0].shape), grad_sync=gs, warmup=2)
+    codes = None
+    if txt is not None:                                                         # different captions per rank
+        tg = torch.Generator()
+        tg.manual_seed(200 + rank)
+        tokens = torch.randint(4, txt.encoder.embed.num_embeddings, (B, 8), generator=tg).to(dev)
+        with torch.no_grad():
+            codes = txt.encode(tokens, [8] * B)[2].detach()
+    step = GraphedTrainStep(gan, optD, optG, losses, Params(), dev, tuple(pool[0].shape), grad_sync=gs, warmup=2,
+                            cond_dim=256 if txt is not None else 0)
     seen = []
     if gs is not None:
         exchange = gs.exchange
@@ -59,7 +103,7 @@ def run(sync):
         gs.exchange = counted
     for i in range(5):                                                          # 2 eager, capture, 2 replays
         del seen[:]
-        lD, lG = step.step(pool[i % 2])
+        lD, lG = step.step(pool[i % 2], codes)
     torch.cuda.synchronize()
     chk = torch.stack([p.detach().double().sum() for p in list(dis.parameters()) + list(gen.parameters())])
     return chk, float(lD), float(lG), (step.n_graphs, ''.join(seen))
@@ -76,6 +120,8 @@ if rank == 0:
     if (args.discrim_steps, args.gen_steps) != (1, 1):
         sched = '; schedule %d:%d, %d graphs and exchanges %s per replayed iteration' % (args.discrim_steps, args.gen_steps,
                                                                                          n_graphs, exchanges)
+    if args.cond:
+        sched += '; text-conditioned, ca_dim %d' % args.ca_dim
     print('DP_CHECK replicas identical after 5 iterations: %s; differs from a solo run by %.3e; lossD %.5f lossG %.5f%s' %
           (same, moved, lD, lG, sched))
     assert same and moved > 1e-6

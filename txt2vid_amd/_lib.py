@@ -211,6 +211,8 @@ SIGNATURES = {
     't2v_tseed_fwd_bn': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P],
     't2v_tseed_fwd_tanh': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     't2v_tseed_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    't2v_ca_fwd': [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    't2v_ca_bwd': [_P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
     't2v_prof_begin': [_I],
     't2v_prof_end': [C.POINTER(C.c_double), _I],
     't2v_version': [],

@@ -2971,3 +2971,84 @@ extern "C" int t2v_wgrad_swap(const float* src, float* dst, int Cout, int Cin, i
     T2V_LAUNCH(wgrad_swap_k, dim3(nblocks((long)Cout * Cin * T)), dim3(256), 0, S_(st), src, dst, Cout, Cin, T, accum);
     return launch_status();
 }
+
+// ---------------------------------------------------------------- conditioning augmentation (StackGAN++ CA, generator input only)
+// h [B, 4D] = fc(s): GLU x = h[:, :2D] * sigmoid(h[:, 2D:]), mu = x[:, :D], logvar = x[:, D:]; c = mu + eps * exp(logvar / 2).
+// The forward writes the whole fc input row [z | c] of the generator and KL = mean over B*D of
+// -0.5 * (1 + logvar - mu^2 - exp(logvar)). ONE workgroup: B*D is a few thousand elements, and each thread sums its strided
+// share in a fixed order, then a wave64 butterfly and a fixed-order pass over the 16 wave partials in LDS: no atomics, the
+// same bits on every run.
+#define CA_THREADS 1024
+__device__ __forceinline__ float ca_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+__global__ __launch_bounds__(CA_THREADS) void ca_fwd_k(const float* __restrict__ h, const float* __restrict__ z,
+                                                       const float* __restrict__ eps, float* __restrict__ out,
+                                                       float* __restrict__ kl, int B, int L, int D) {
+    __shared__ float red[CA_THREADS / 64];
+    const int W = L + D;
+    const long nz = (long)B * L;
+    for (long i = threadIdx.x; i < nz; i += CA_THREADS) {
+        const long r = i / L;
+        out[r * W + (i - r * L)] = z[i];
+    }
+    const long n = (long)B * D;
+    float acc = 0.f;
+    for (long i = threadIdx.x; i < n; i += CA_THREADS) {
+        const long r = i / D;
+        const int j = (int)(i - r * D);
+        const float* hr = h + r * 4 * D;
+        const float mu = hr[j] * ca_sigmoid(hr[2 * D + j]);
+        const float lv = hr[D + j] * ca_sigmoid(hr[3 * D + j]);
+        out[r * W + L + j] = mu + eps[i] * expf(0.5f * lv);
+        acc += -0.5f * (1.f + lv - mu * mu - expf(lv));
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int w = 0; w < CA_THREADS / 64; ++w) s += red[w];
+        kl[0] = s / (float)n;
+    }
+}
+
+// dL/dh from dL/d[z | c] (only the c columns are read; may be null) and dL/dKL (device scalar, may be null) times kl_coeff.
+// d KL / d mu = mu / (B*D), d KL / d logvar = (exp(logvar) - 1) / (2*B*D); c = mu + eps * exp(logvar / 2); then the GLU.
+__global__ __launch_bounds__(256) void ca_bwd_k(const float* __restrict__ gout, const float* __restrict__ gkl, float kl_coeff,
+                                                const float* __restrict__ h, const float* __restrict__ eps, float* __restrict__ gh,
+                                                int B, int L, int D) {
+    const long n = (long)B * D;
+    const float gk = gkl ? gkl[0] * kl_coeff / (float)n : 0.f;
+    const int W = L + D;
+    GRID_STRIDE(i, n) {
+        const long r = i / D;
+        const int j = (int)(i - r * D);
+        const float* hr = h + r * 4 * D;
+        const float am = hr[j], sm = ca_sigmoid(hr[2 * D + j]);
+        const float al = hr[D + j], sl = ca_sigmoid(hr[3 * D + j]);
+        const float mu = am * sm, lv = al * sl;
+        const float gc = gout ? gout[r * W + L + j] : 0.f;
+        const float dmu = gc + gk * mu;
+        const float dlv = gc * eps[i] * 0.5f * expf(0.5f * lv) + gk * 0.5f * (expf(lv) - 1.f);
+        float* g = gh + r * 4 * D;
+        g[j] = dmu * sm;
+        g[2 * D + j] = dmu * am * sm * (1.f - sm);
+        g[D + j] = dlv * sl;
+        g[3 * D + j] = dlv * al * sl * (1.f - sl);
+    }
+}
+
+extern "C" int t2v_ca_fwd(const float* h, const float* z, const float* eps, float* out, float* kl, int B, int L, int D, void* st) {
+    if (!h || !eps || !out || !kl || B < 1 || D < 1 || L < 0 || (L > 0 && !z)) return T2V_EINVAL;
+    if ((long)B * (L + D) > 0x7fffffffL || (long)B * 4 * D > 0x7fffffffL) return T2V_EINVAL;
+    T2V_LAUNCH(ca_fwd_k, dim3(1), dim3(CA_THREADS), 0, S_(st), h, z, eps, out, kl, B, L, D);
+    return launch_status();
+}
+
+extern "C" int t2v_ca_bwd(const float* gout, const float* gkl, float kl_coeff, const float* h, const float* eps, float* gh, int B,
+                          int L, int D, void* st) {
+    if (!h || !eps || !gh || B < 1 || D < 1 || L < 0) return T2V_EINVAL;
+    if ((long)B * (L + D) > 0x7fffffffL || (long)B * 4 * D > 0x7fffffffL) return T2V_EINVAL;
+    T2V_LAUNCH(ca_bwd_k, dim3(nblocks((long)B * D)), dim3(256), 0, S_(st), gout, gkl, kl_coeff, h, eps, gh, B, L, D);
+    return launch_status();
+}

@@ -37,8 +37,13 @@ class CondGan(object):
         self.discrim_lambdas = discrim_lambdas
         self.gp_scale = gp_scale          # data-parallel: world_size, else 1
 
-    def _discrim_weighted_sum(self, losses):
-        """cond_gan.py:26-31: mean over discriminators, or lambda-weighted sum."""
+    def _discrim_weighted_sum(self, losses, kl=None, kl_coeff=0.0):
+        """cond_gan.py:26-31: mean over discriminators, or lambda-weighted sum. `kl`: the generator's conditioning-augmentation
+        KL term (a 0-d tensor; not in the reference), added with weight `kl_coeff` by the same launch."""
+        losses = list(losses)
+        weights = [1.0 / len(losses)] * len(losses) if self.discrim_lambdas is None else list(self.discrim_lambdas)
+        if kl is not None:
+            return TF.scalar_sum(losses + [kl], weights=weights + [kl_coeff])
         if self.discrim_lambdas is None:
             return TF.scalar_mean(losses)
         return TF.scalar_sum(losses, weights=self.discrim_lambdas)
@@ -149,11 +154,12 @@ class CondGan(object):
             l = TF.scalar_sum([l, gp], weights=[1.0, gp_lambda])
         return l, fake_pred, real_pred
 
-    def gen_step_fused(self, fake=None, real=None, cond=None, loss=None, draw_perm=True):
+    def gen_step_fused(self, fake=None, real=None, cond=None, loss=None, draw_perm=True, kl=None, kl_coeff=0.0):
         """`all_discrim_forward(real)` + `gen_step(fake, real_pred)` (trainer.py:247-263) as ONE lock-step pass
         of the frozen, freshly updated D over the generated AND the (detached) real clips: identical values,
         half the launches; the backward only runs through the generated half. `draw_perm=False`: a later G step of
-        the same iteration, whose real_pred the reference does not recompute (no permutation is drawn)."""
+        the same iteration, whose real_pred the reference does not recompute (no permutation is drawn). `kl`, `kl_coeff`:
+        the generator's conditioning-augmentation term, as in `gen_step`."""
         self.gen.zero_grad()
         if self.cond_encoder is not None:
             self.cond_encoder.zero_grad()
@@ -178,16 +184,18 @@ class CondGan(object):
                 lu = _mean_over_levels(loss, [ff[0] for ff in fk], [rr[0].detach() for rr in rl])
                 lc = _mean_over_levels(loss, [ff[1] for ff in fk], [rr[1].detach() for rr in rl])
                 losses.append(TF.scalar_sum([lc, lu], weights=[0.5, 0.5]))
-        return self._discrim_weighted_sum(losses)
+        return self._discrim_weighted_sum(losses, kl, kl_coeff)
 
     def can_fuse_gen_step(self, fake, real):
         return all(_fusable(d, real, fake) and 2 * len(fake) <= TF.MAX_GROUPS for d in self.discrims)
 
-    def gen_step(self, fake=None, real_pred=None, cond=None, loss=None):
+    def gen_step(self, fake=None, real_pred=None, cond=None, loss=None, kl=None, kl_coeff=0.0):
         """cond_gan.py:90-118. The uncond branch uses `ff[0]` (the intended semantics; the reference
         passes the whole tuple and crashes, SURVEY §8a defect 1). D's parameters are frozen for this
         forward: the reference computes their gradients here and zeroes them before they are ever used
-        (cond_gan.py:157-158), so skipping the D weight-gradient kernels leaves every result identical."""
+        (cond_gan.py:157-158), so skipping the D weight-gradient kernels leaves every result identical.
+        `kl` (0-d, or None): the KL term of the generator's conditioning augmentation (not in the reference); the loss becomes
+        the adversarial loss + kl_coeff * kl."""
         self.gen.zero_grad()
         if self.cond_encoder is not None:
             self.cond_encoder.zero_grad()
@@ -207,7 +215,7 @@ class CondGan(object):
                 lu = TF.scalar_mean([loss(fake=ff[0], real=rr[0]) for ff, rr in zip(fake_cc, r)])
                 lc = TF.scalar_mean([loss(fake=ff[1], real=rr[1]) for ff, rr in zip(fake_cc, r)])
                 losses.append(TF.scalar_sum([lc, lu], weights=[0.5, 0.5]))
-        return self._discrim_weighted_sum(losses)
+        return self._discrim_weighted_sum(losses, kl, kl_coeff)
 
     def all_discrim_forward(self, fake=None, real=None, cond=None, loss=None, gp_lambda=-1):
         """cond_gan.py:121-154."""

@@ -100,6 +100,12 @@ class TrainStep(object):
         self.device, self.end2end, self.grad_sync = device, end2end, grad_sync
         self.lD = self.lG = self.fake = self.xs = self.conds = None
         self._z = self._real_pred = None
+        # conditioning augmentation of the generator (MultiScaleGen(ca_dim > 0), not in the reference): every G step's loss gains
+        # ca_kl_coeff * KL of that step's forward; lKL totals the KL over the G steps like lG (device-side)
+        gen = getattr(gan, 'gen', None)
+        self.ca = bool(getattr(gen, 'ca_dim', 0))
+        self.kl_coeff = float(getattr(gen, 'ca_kl_coeff', 0.0)) if self.ca else 0.0
+        self.lKL = self._kl = None
         self._fused = False
         self._one = None                  # dL/dL = 1 for both backward passes: one persistent 0-d tensor (no fill launch per pass)
         # the store_false quirk of --no_mean_*_loss (trainer.py:236-237,260-261): the loss of every step is divided by the step
@@ -144,7 +150,11 @@ class TrainStep(object):
         return TF.scalar_sum([total, loss], weights=[1.0, scale])
 
     def _forward_g(self):
-        return self.gan(self._z, cond=self.conds[0] if self.conds is not None else None)
+        cond = self.conds[0] if self.conds is not None else None
+        if self.ca:
+            fake, self._kl = self.gan(self._z, cond=cond, return_kl=True)      # CA draws this forward's eps before its phases
+            return fake
+        return self.gan(self._z, cond=cond)
 
     def _d_step(self, arm=True):
         p = self.params
@@ -159,7 +169,7 @@ class TrainStep(object):
     def part_d(self, x, cond):
         """D part 0: pyramid, z, G forward and the first D step."""
         p = self.params
-        self.lD = self.lG = self._real_pred = None
+        self.lD = self.lG = self._real_pred = self.lKL = None
         self._arm_sink()
         self.xs, self.conds = multiscale_data(x, cond, p.frame_sizes, p.subsample_input)
         self._z = TF.draws.z(x.size(0), self.gan.gen.latent_size, self.device)       # CPU generator, then copy (parity)
@@ -180,7 +190,7 @@ class TrainStep(object):
         # that is ever used, so none is recorded (identical results, SURVEY §7 "wasted work").
         self._fused = not self.end2end and self.gan.can_fuse_gen_step(self.fake, self.xs)
         if self._fused:
-            loss = self.gan.gen_step_fused(fake=self.fake, real=self.xs, cond=self.conds, loss=self.losses.gen_loss)
+            loss = self.gan.gen_step_fused(fake=self.fake, real=self.xs, cond=self.conds, loss=self.losses.gen_loss, **self._kl_args())
         else:
             if self.end2end:
                 _, _, real_pred = self.gan.all_discrim_forward(real=self.xs, cond=self.conds, fake=None, loss=None)
@@ -189,7 +199,8 @@ class TrainStep(object):
                     _, _, real_pred = self.gan.all_discrim_forward(real=self.xs, cond=self.conds, fake=None, loss=None)
             if self.n_g > 1:
                 self._real_pred = real_pred
-            loss = self.gan.gen_step(fake=self.fake, real_pred=real_pred, cond=self.conds, loss=self.losses.gen_loss)
+            loss = self.gan.gen_step(fake=self.fake, real_pred=real_pred, cond=self.conds, loss=self.losses.gen_loss,
+                                     **self._kl_args())
         self._g_backward(loss, last=self.n_g == 1)
 
     def part_g_more(self, last):
@@ -201,16 +212,23 @@ class TrainStep(object):
         self.fake = self._forward_g()
         if self._fused:
             loss = self.gan.gen_step_fused(fake=self.fake, real=self.xs, cond=self.conds, loss=self.losses.gen_loss,
-                                           draw_perm=False)
+                                           draw_perm=False, **self._kl_args())
         else:
-            loss = self.gan.gen_step(fake=self.fake, real_pred=self._real_pred, cond=self.conds, loss=self.losses.gen_loss)
+            loss = self.gan.gen_step(fake=self.fake, real_pred=self._real_pred, cond=self.conds, loss=self.losses.gen_loss,
+                                     **self._kl_args())
         self._g_backward(loss, last)
+
+    def _kl_args(self):
+        return {'kl': self._kl, 'kl_coeff': self.kl_coeff} if self.ca else {}
 
     def _g_backward(self, loss, last):
         # --end2end: real_pred and the sentence code keep their graphs for the next G step (trainer.py:262)
         loss.backward(gradient=self._root(loss, self.g_scale), retain_graph=self.end2end and not last)
         TF.grad_sink_flush()
         self.lG = self._total(self.lG, loss, self.g_scale)
+        if self.ca:
+            self.lKL = self._total(self.lKL, self._kl, self.g_scale)
+            self._kl = None
         if last:
             self._real_pred = None
 
@@ -270,7 +288,8 @@ class GraphedTrainStep(object):
         N, M = self.ts.n_d, self.ts.n_g
         self.draws = TF.StaticDraws(device, batch_shape[0], gan.gen.latent_size, n_levels, n_gen_phases=n_levels - 1,
                                     gp=params.gp_lambda > 0, subsample_input=params.subsample_input,
-                                    n_perms=(N + 1) * len(gan.discrims) if cond_dim else 0, n_d_steps=N, n_g_steps=M)
+                                    n_perms=(N + 1) * len(gan.discrims) if cond_dim else 0, n_d_steps=N, n_g_steps=M,
+                                    ca_dim=getattr(gan.gen, 'ca_dim', 0) if cond_dim else 0)
         self.x = torch.empty(batch_shape, device=device, dtype=torch.float32)
         # conditional path: the sentence code is computed outside the graphs (its sequence length varies) into a fixed buffer
         self.cond = torch.empty((batch_shape[0], cond_dim), device=device, dtype=torch.float32) if cond_dim else None
@@ -290,6 +309,7 @@ class GraphedTrainStep(object):
             opt.make_capturable(self.device)
         # drop every reference into the previous iteration's autograd graph before capturing
         self.ts.lD = self.ts.lG = self.ts.fake = self.ts.xs = self.ts.conds = self.ts._real_pred = None
+        self.ts.lKL = self.ts._kl = None
         torch.cuda.synchronize()
         self.draws.rewind()
         gs = self.grad_sync
@@ -474,6 +494,7 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
     ensure_exists(params.out_samples)
     gen_loss = RollingAvg(window_size=params.loss_window_size)
     discrim_loss = RollingAvg(window_size=params.loss_window_size)
+    kl_loss = RollingAvg(window_size=params.loss_window_size) if getattr(gan.gen, 'ca_dim', 0) else None     # conditioning augmentation
     avg_iter = RollingAvg(window_size=max(1, params.log_period))
     avg_load = RollingAvg(window_size=max(1, params.log_period))
     load_watch, iter_watch = Stopwatch(), Stopwatch()
@@ -525,27 +546,36 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 # Read the losses ONE iteration late, through a pinned buffer and an event: the host goes on to prepare
                 # and launch the next iteration while this one runs (the replay overwrites its loss scalars, hence the
                 # copies). The rolling averages lag by one iteration.
+                lKL = graphed.ts.lKL
                 if loss_ring is None:
-                    loss_ring = [(torch.empty(2, device=lD.device), torch.empty(2).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+                    loss_ring = [(torch.empty(3, device=lD.device), torch.empty(3).pin_memory(), torch.cuda.Event()) for _ in range(2)]
                 dbuf, hbuf, ev = loss_ring[iteration & 1]
                 if _X_BY_MEMCPY:
                     TF.copy_into(lD.reshape(1), dbuf[0:1])
                     TF.copy_into(lG.reshape(1), dbuf[1:2])
+                    if lKL is not None:
+                        TF.copy_into(lKL.reshape(1), dbuf[2:3])
                     hbuf.copy_(dbuf, non_blocking=True)
                 else:                                    # copy kernels writing the pinned buffer in place: no copy-engine hop behind the graph
                     TF._copy2d(lD.reshape(1), 0, 1, hbuf, 0, 1, 1, 1)
                     TF._copy2d(lG.reshape(1), 0, 1, hbuf, 1, 1, 1, 1)
+                    if lKL is not None:
+                        TF._copy2d(lKL.reshape(1), 0, 1, hbuf, 2, 1, 1, 1)
                 ev.record()
                 if pending is not None:
                     pending[1].synchronize()
                     discrim_loss.update(float(pending[0][0]))
                     gen_loss.update(float(pending[0][1]))
+                    if kl_loss is not None:
+                        kl_loss.update(float(pending[0][2]))
                 pending = (hbuf, ev)
             else:
-                lD, lG, fake, xs = train_iteration(gan, x, cond, optD, optG, losses, params, device, end2end=end2end,
-                                                   grad_sync=grad_sync)
+                ts = TrainStep(gan, optD, optG, losses, params, device, end2end, grad_sync)       # (= train_iteration)
+                lD, lG, fake, xs = ts.run(x, cond)
                 discrim_loss.update(float(lD))
                 gen_loss.update(float(lG))
+                if kl_loss is not None:
+                    kl_loss.update(float(ts.lKL))
             # checkpoint: the reference tests `save_example_period` here (trainer.py:269) and never reads
             # --save_model_period; the intended flag is used (SURVEY §8a defect 3).
             if writer and ((iteration == 1 and params.save_initial) or (params.save_model_period > 0 and
@@ -562,6 +592,9 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                        '%.4f sec/batch load' % (epoch, num_epoch, i, len(dataset), iteration, discrim_loss.get(),
                                                 gen_loss.get(), torch.cuda.max_memory_allocated() / 1e9,
                                                 torch.cuda.max_memory_reserved() / 1e9, avg_iter.get(), avg_load.get()))
+                if kl_loss is not None:
+                    status('Iter %d, KL (conditioning augmentation, inside Loss_G with weight %g): %.4f' %
+                           (iteration, gan.gen.ca_kl_coeff, kl_loss.get()))
                 torch.cuda.reset_peak_memory_stats()
             if writer and params.save_example_period > 0 and ((iteration == 1 and params.save_initial_examples) or
                                                               iteration % params.save_example_period == 0):

@@ -31,14 +31,28 @@ class MultiScaleGen(nn.Module):
     _cond_variant = False
 
     def __init__(self, latent_size=256, width=128, height=128, num_channels=3, additional_blocks=[64, 32, 32],
-                 fm_channels=1024, num_frames=16, cond_dim=0, no_lstm=False):
+                 fm_channels=1024, num_frames=16, cond_dim=0, no_lstm=False, ca_dim=0, ca_kl_coeff=2.0):
         super().__init__()
+        # ca_dim > 0: StackGAN++ conditioning augmentation turns the sentence code into c [B, ca_dim] in front of fc (models/ca.py;
+        # not in the reference, off by default). ca_dim = 0 builds exactly the reference's module.
+        self.ca_dim, self.ca_kl_coeff = int(ca_dim), float(ca_kl_coeff)
+        if self.ca_dim < 0:
+            raise ValueError('ca_dim must be >= 0 (got %d)' % self.ca_dim)
+        if self.ca_dim and not self._cond_variant:
+            raise ValueError('ca_dim > 0 (conditioning augmentation) needs the text-conditioned generator '
+                             'txt2vid.models.tganv2_cond.gen.MultiScaleGen')
+        if self.ca_dim and cond_dim < 1:
+            raise ValueError('ca_dim > 0 (conditioning augmentation) needs a sentence code (cond_dim > 0): it cannot run with '
+                             '--dont_use_sent')
         self.subsample = Subsample()
         # the recurrent state is a [fm_channels, height/64, width/64] map per sample: 1x1 for 64x64 frames, 2x2 for 128x128
         self.latent_size, self.fm_channels, self.latent_plane_ch = latent_size, fm_channels, fm_channels
         self.fm_width, self.fm_height = max(1, width // 64), max(1, height // 64)
         self.fm_size = self.latent_plane_ch * self.fm_height * self.fm_width
-        self.fc = Linear(latent_size + (cond_dim if self._cond_variant else 0), self.fm_size)
+        if self.ca_dim:
+            from ..ca import CondAugmentation
+            self.ca = CondAugmentation(cond_dim, self.ca_dim)
+        self.fc = Linear(latent_size + ((self.ca_dim or cond_dim) if self._cond_variant else 0), self.fm_size)
         self.no_lstm = no_lstm
         if no_lstm:
             # TGAN-v1's frame-seed generator instead of the ConvLSTM: always 16 frames, whatever num_frames says (gen.py:40-43)
@@ -68,9 +82,26 @@ class MultiScaleGen(nn.Module):
         centre = (k // 2) * k + k // 2
         return {m.weight: [centre] for m in (cell.Wxi, cell.Wxf, cell.Wxc, cell.Wxo, cell.Whi, cell.Whf, cell.Whc, cell.Who)}
 
-    def forward(self, x, cond=None, return_abstract_maps=False, output_blocks=None):
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """A checkpoint written with conditioning augmentation (`ca.fc.*` keys) loads only into a generator built with the same
+        ca_dim, and one without into one without: a clear error instead of a bare shape mismatch on fc.weight."""
+        w = state_dict.get('ca.fc.weight')
+        got = 0 if w is None else int(w.shape[0]) // 4
+        if got != self.ca_dim:
+            raise ValueError('generator checkpoint %s conditioning augmentation (ca_dim=%d) but this generator was built with '
+                             'ca_dim=%d: pass the same ca_dim in the --G spec' % ('has' if got else 'has no', got, self.ca_dim))
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    def forward(self, x, cond=None, return_abstract_maps=False, output_blocks=None, return_kl=False):
+        """`return_kl`: also return the conditioning augmentation's KL term (a 0-d device tensor; None without CA) as the last
+        element: (rendered, kl) or (rendered, abstract, kl)."""
         from ... import functional as TF
-        if cond is not None:
+        kl = None
+        if self.ca_dim:
+            if cond is None:
+                raise ValueError('conditioning augmentation (ca_dim=%d) needs the sentence code' % self.ca_dim)
+            x, kl = self.ca(x, cond)                           # [z | c] in one launch, eps drawn before the Subsample phases
+        elif cond is not None:
             x = TF.cat_features(x, cond)
         x = self.fc(x)
         if self.no_lstm:
@@ -100,8 +131,8 @@ class MultiScaleGen(nn.Module):
                     r = self.render_blocks[i](x)
                 rendered.append(TF.frames_to_video(r, num_frames))           # [b,C,T,H,W]
         if return_abstract_maps:
-            return rendered, abstract
-        return rendered
+            return (rendered, abstract, kl) if return_kl else (rendered, abstract)
+        return (rendered, kl) if return_kl else rendered
 
     def subsample_frames(self, x, num_frames):
         """`Subsample` applied on the merged-frames layout: keeps samples ::2 and frames bt::2
