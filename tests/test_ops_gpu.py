@@ -57,6 +57,49 @@ def test_conv_fwd_bwd(xs, cout, k):
     close(bd.grad, br.grad, rtol=2e-4, atol=2e-4)
 
 
+@pytest.mark.parametrize('xs,cout,k', [((2, 24, 3, 6, 5), 40, (3, 3, 3)), ((7, 48), 20, (1, 1, 1))])
+def test_single_tensor_entry_points_equal_a_group_of_one(xs, cout, k):
+    """The single-tensor C entry points (`t2v_conv_fwd`, `t2v_conv_wgrad`, `t2v_channel_sum` and their size queries), which
+    the Python package no longer calls, against the grouped launchers on a one-member list: bit for bit, because the C
+    wrappers forward to the same functions with the same arguments (the channel sum walks the same elements in the same
+    order). fp32 only: the single entry points have no bf16 form."""
+    import ctypes as C
+    from txt2vid_amd import functional as TF
+    from txt2vid_amd._lib import lib
+    assert TF.CONV_PRECISION == 'fp32'
+    p, st = TF._p, TF._stream
+
+    def buf(n):
+        return torch.empty((max(int(n), 1),), device=dev())
+    x = TF._as5(rnd(1, *xs).to(dev()))
+    N, cin = xs[0], xs[1]
+    w = (rnd(2, cout, cin, *k) * 0.1).to(dev())
+    b = rnd(3, cout).to(dev())
+    gy = rnd(4, N, cout, *x.shape[2:]).to(dev())
+    g = TF.conv_geom(N, cin, x.shape[2], x.shape[3], x.shape[4], cout, *k)
+
+    wp = torch.empty((len(g.taps), cin * cout), device=dev())
+    assert lib().t2v_pack_weight(p(w), p(wp), cout, cin, g.T, g.taps_c, len(g.taps), 0, st()) == 0
+    nws = lib().t2v_conv_fwd_ws_floats(C.byref(g.cg))
+    assert nws >= 0
+    y = torch.empty((N, cout) + tuple(x.shape[2:]), device=dev())
+    assert lib().t2v_conv_fwd(p(x), p(wp), p(b), p(y), p(buf(nws)), C.byref(g.cg), TF.FLAG_BIAS, st()) == 0
+    assert torch.equal(y, TF.conv_group_raw([x], w, b)[0])
+
+    nslab = lib().t2v_conv_wgrad_slab_floats(C.byref(g.cg), g.T)
+    assert nslab > 0
+    dw = torch.empty(tuple(w.shape), device=dev())
+    assert lib().t2v_conv_wgrad(p(x), p(gy), p(dw), p(buf(nslab)), C.byref(g.cg), g.taps_c, g.T, 0, st()) == 0
+    assert torch.equal(dw, TF.conv_group_wgrad_raw([x], [gy], tuple(w.shape)))
+
+    S = gy.numel() // (N * cout)
+    ncs = lib().t2v_channel_sum_ws_floats(N, cout, S)
+    assert ncs >= 0
+    db = torch.empty((cout,), device=dev())
+    assert lib().t2v_channel_sum(p(gy), p(db), p(buf(ncs)), N, cout, S, 0, st()) == 0
+    assert torch.equal(db, TF.channel_sum_group_raw([gy]))
+
+
 @pytest.mark.parametrize('case', GROUPED_CASES, ids=[c[0] for c in GROUPED_CASES])
 def test_conv_grouped_at_benchmark_size(case):
     """The discriminator's grouped launches at the size bench.py runs them (BASELINE configs[1], per-GPU batch 32: the 8

@@ -34,6 +34,6 @@ def timeit(fn, name):
     print('%-10s M=%-7d Cin=%-4d Cout=%-4d taps=%-2d %8.1f us  %6.1f TFLOP/s' % (name, N * D * H * W, Cin, Cout, taps, dt * 1e6, flops / dt / 1e12))
 
 
-timeit(lambda: TF.conv_fwd_raw(x, w), 'fwd')
-timeit(lambda: TF.conv_dgrad_raw(gy, w), 'dgrad')
-timeit(lambda: TF.conv_wgrad_raw(x, gy, tuple(w.shape)), 'wgrad')
+timeit(lambda: TF.conv_group_raw([x], w), 'fwd')
+timeit(lambda: TF.conv_group_raw([gy], w, mode=1), 'dgrad')
+timeit(lambda: TF.conv_group_wgrad_raw([x], [gy], tuple(w.shape)), 'wgrad')

@@ -8,6 +8,9 @@ The discriminator ops are *closed under differentiation*: the backward of each F
 written with Functions of this module, so `torch.autograd.grad(..., create_graph=True)` — the
 gradient penalty of txt2vid/gan/losses.py:178 — yields a graph whose own backward again runs only
 these kernels (conv fwd <-> dgrad <-> wgrad form a closed triple).
+
+There is ONE convolution triple, the grouped one (`ConvG` / `ConvDgradG` / `ConvDgradMaskG` / `ConvWgradG` over
+`conv_group_raw` / `conv_group_wgrad_raw`): `conv`, `relu_conv` and `linear` on a single tensor are groups of one.
 """
 import contextlib
 import ctypes as C
@@ -295,7 +298,7 @@ def _to_sink_wb(w, b, xs, gys, relu_in, even_frames=False):
     wbase = w._base if w._base is not None else w
     if id(wbase) not in _grad_sink.slots or id(b) not in _grad_sink.slots:
         return False, None, None
-    deferred = _grad_sink.defer and _wgrad_bias_fused(xs, tuple(w.shape))
+    deferred = _grad_sink.defer
     wflat, wacc = _grad_sink.take(wbase, deferred)
     bflat, bacc = _grad_sink.take(b, deferred)
     if deferred:
@@ -358,7 +361,7 @@ def _wtag(base, ptr=None):
 # ------------------------------------------------------------------------------------------------
 
 class _Geom(object):
-    __slots__ = ('cg', 'taps', 'taps_c', 'T', 'mask', 'kshape', 'ws_floats')
+    __slots__ = ('cg', 'taps', 'taps_c', 'T', 'mask', 'kshape')
 
 
 _geom_cache = {}
@@ -389,7 +392,6 @@ def conv_geom(N, Cin, D, H, W, Cout, kD, kH, kW):
     g.cg, g.taps, g.T, g.kshape = cg, taps, kD * kH * kW, (kD, kH, kW)
     g.taps_c = (C.c_int32 * len(taps))(*taps)
     g.mask = sum(1 << t for t in taps)
-    g.ws_floats = None
     _geom_cache[key] = g
     return g
 
@@ -574,14 +576,14 @@ def packed_fused(ws, ts, mode):
 
 
 def conv_packed_raw(x5, wp, cin, cout, k, bias=None, out=None, accum=False):
-    """Convolution with an explicitly packed weight (fused gates): wp holds the taps of this geometry in order."""
+    """Convolution with an explicitly packed fp32 weight (fused gates): wp holds the taps of this geometry in order."""
     x5 = _c(x5)
-    g = conv_geom(x5.shape[0], cin, x5.shape[2], x5.shape[3], x5.shape[4], cout, k[0], k[1], k[2])
     y = out if out is not None else torch.empty((x5.shape[0], cout) + tuple(x5.shape[2:]), device=x5.device, dtype=torch.float32)
+    arr, _ = _conv_table([x5], [y], cin, cout, k)          # (one member: tap j sits in packed slot j)
     flags = (FLAG_BIAS if bias is not None else 0) | (FLAG_ACCUM if accum else 0)
-    check(lib().t2v_conv_fwd(_p(x5), _p(wp), _p(bias), _p(y), _p(_conv_ws(g, x5.device)), C.byref(g.cg), flags, _stream()),
-          't2v_conv_fwd')
-    return y, g
+    check(lib().t2v_conv_fwd_grouped(arr, 1, cin, cout, _p(wp), _p(bias), _p(_fwd_workspace(arr, 1, cin, cout, x5.device)), flags, _stream()),
+          't2v_conv_fwd_grouped')
+    return y
 
 
 def _as5(t):
@@ -593,67 +595,6 @@ def _as5(t):
     if t.dim() == 2:
         return t.view(t.size(0), t.size(1), 1, 1, 1)
     raise ValueError('expected a 2-, 4- or 5-D tensor')
-
-
-def _geom_for(x5, w5):
-    return conv_geom(x5.shape[0], w5.shape[1], x5.shape[2], x5.shape[3], x5.shape[4], w5.shape[0],
-                     w5.shape[2], w5.shape[3], w5.shape[4])
-
-
-def _conv_ws(g, device):
-    """split-K workspace for this geometry (None when the launch plan does not split)."""
-    n = getattr(g, 'ws_floats', None)
-    if n is None:
-        n = int(lib().t2v_conv_fwd_ws_floats(C.byref(g.cg)))
-        if n < 0:
-            raise RuntimeError('bad conv geometry')
-        g.ws_floats = n
-    return torch.empty((n,), device=device, dtype=torch.float32) if n > 0 else None
-
-
-def conv_fwd_raw(x5, w5, bias=None, relu_in=False, out=None, accum=False):
-    if CONV_PRECISION == 'bf16':
-        return conv_group_raw([x5], w5, bias, relu_in, 0, outs=None if out is None else [out], accum=accum)[0]
-    x5, w5 = _c(x5), _c(w5)
-    g = _geom_for(x5, w5)
-    wp = packed_weight(w5, g, 0)
-    y = out if out is not None else torch.empty((x5.shape[0], w5.shape[0]) + tuple(x5.shape[2:]), device=x5.device,
-                                                dtype=torch.float32)
-    flags = (FLAG_BIAS if bias is not None else 0) | (FLAG_RELU_IN if relu_in else 0) | (FLAG_ACCUM if accum else 0)
-    check(lib().t2v_conv_fwd(_p(x5), _p(wp), _p(bias), _p(y), _p(_conv_ws(g, x5.device)), C.byref(g.cg), flags, _stream()),
-          't2v_conv_fwd')
-    return y
-
-
-def conv_dgrad_raw(gy5, w5, out=None, accum=False):
-    """gx[N,Cin,...] = sum_taps,co gy * w (mirrored): the forward kernel on the mode-1 packed weight."""
-    if CONV_PRECISION == 'bf16':
-        return conv_group_raw([gy5], w5, None, False, 1, outs=None if out is None else [out], accum=accum)[0]
-    gy5, w5 = _c(gy5), _c(w5)
-    Cout, Cin = w5.shape[0], w5.shape[1]
-    # geometry of the transposed problem: input channels = Cout, output channels = Cin
-    gt = conv_geom(gy5.shape[0], Cout, gy5.shape[2], gy5.shape[3], gy5.shape[4], Cin, w5.shape[2], w5.shape[3], w5.shape[4])
-    wp = packed_weight(w5, gt, 1)
-    gx = out if out is not None else torch.empty((gy5.shape[0], Cin) + tuple(gy5.shape[2:]), device=gy5.device,
-                                                 dtype=torch.float32)
-    check(lib().t2v_conv_fwd(_p(gy5), _p(wp), None, _p(gx), _p(_conv_ws(gt, gy5.device)), C.byref(gt.cg),
-                             FLAG_ACCUM if accum else 0, _stream()), 't2v_conv_fwd(dgrad)')
-    return gx
-
-
-def conv_wgrad_raw(x5, gy5, wshape, relu_in=False, out=None, accum=False):
-    if CONV_PRECISION == 'bf16':
-        return conv_group_wgrad_raw([x5], [gy5], wshape, relu_in, out=out, accum=accum)
-    x5, gy5 = _c(x5), _c(gy5)
-    g = conv_geom(x5.shape[0], wshape[1], x5.shape[2], x5.shape[3], x5.shape[4], wshape[0], wshape[2], wshape[3], wshape[4])
-    n = lib().t2v_conv_wgrad_slab_floats(C.byref(g.cg), g.T)
-    if n <= 0:
-        raise RuntimeError('bad wgrad geometry')
-    slab = torch.empty((n,), device=x5.device, dtype=torch.float32)
-    dw = out if out is not None else torch.empty(tuple(wshape), device=x5.device, dtype=torch.float32)
-    check(lib().t2v_conv_wgrad(_p(x5), _p(gy5), _p(dw), _p(slab), C.byref(g.cg), g.taps_c, g.T,
-                               (FLAG_RELU_IN if relu_in else 0) | (FLAG_ACCUM if accum else 0), _stream()), 't2v_conv_wgrad')
-    return dw
 
 
 def channel_sum_raw(t5, out=None, accum=False):
@@ -668,154 +609,10 @@ def channel_sum_raw(t5, out=None, accum=False):
     return out
 
 
-class Conv(Function):
-    """y = conv(x, w) + b  (stride 1, same padding; 5-D tensors). nn.Conv3d/Conv2d/Linear forward."""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        ctx.save_for_backward(x, w)
-        ctx.has_bias, ctx.bias = b is not None, b
-        return conv_fwd_raw(x, w, b)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = ConvDgrad.apply(gy, w)
-        if _param_grads_enabled:
-            both = False
-            if ctx.needs_input_grad[1] and ctx.has_bias and ctx.needs_input_grad[2]:
-                both, gw, gb = _to_sink_wb(w, ctx.bias, [x], [gy], False)
-            if not both:
-                if ctx.needs_input_grad[1]:
-                    done, gw = _to_sink_w(w, [x], [gy], False)
-                    if not done:
-                        gw = ConvWgrad.apply(x, gy, tuple(w.shape))
-                if ctx.has_bias and ctx.needs_input_grad[2]:
-                    done, gb = _to_sink(ctx.bias, lambda out, acc: channel_sum_raw(gy, out=out, accum=acc))
-                    if not done:
-                        gb = ChannelSum.apply(gy)
-        return gx, gw, gb
-
-
-class ConvDgrad(Function):
-    """gx = conv_transpose(gy, w): the data gradient as a first-class differentiable op."""
-
-    @staticmethod
-    def forward(ctx, gy, w):
-        ctx.save_for_backward(gy, w)
-        return conv_dgrad_raw(gy, w)
-
-    @staticmethod
-    def backward(ctx, ggx):
-        gy, w = ctx.saved_tensors
-        d_gy = d_w = None
-        if ctx.needs_input_grad[0]:
-            d_gy = Conv.apply(ggx, w, None)
-        if ctx.needs_input_grad[1] and _param_grads_enabled:
-            done, d_w = _to_sink_w(w, [ggx], [gy], False)
-            if not done:
-                d_w = ConvWgrad.apply(ggx, gy, tuple(w.shape))
-        return d_gy, d_w
-
-
-class ConvWgrad(Function):
-    """gw = sum_m gy (x) x_shifted: the weight gradient as a differentiable op."""
-
-    @staticmethod
-    def forward(ctx, x, gy, wshape):
-        ctx.save_for_backward(x, gy)
-        ctx.wshape = wshape
-        return conv_wgrad_raw(x, gy, wshape)
-
-    @staticmethod
-    def backward(ctx, ggw):
-        x, gy = ctx.saved_tensors
-        d_x = d_gy = None
-        if ctx.needs_input_grad[0]:
-            d_x = ConvDgrad.apply(gy, ggw)
-        if ctx.needs_input_grad[1]:
-            d_gy = Conv.apply(x, ggw, None)
-        return d_x, d_gy, None
-
-
-class ReluConv(Function):
-    """y = conv(relu(x), w) + b with the ReLU applied while gathering (no activated copy is written):
-    the `ReLU -> conv` pairs of DownBlock / res_block (layers.py:230-233, resnet3d.py:14-15).
-    Backward: gx = dgrad(gy, w) * [x > 0];  gw = wgrad(relu(x), gy) with the same fused gather."""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        ctx.save_for_backward(x, w)
-        ctx.has_bias, ctx.bias = b is not None, b
-        return conv_fwd_raw(x, w, b, relu_in=True)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = ConvDgradMaskG.apply(w, 1, gy, x)[0]          # dgrad(gy, w) * [x > 0] in one launch
-        if _param_grads_enabled:
-            both = False
-            if ctx.needs_input_grad[1] and ctx.has_bias and ctx.needs_input_grad[2]:
-                both, gw, gb = _to_sink_wb(w, ctx.bias, [x], [gy], True)
-            if not both:
-                if ctx.needs_input_grad[1]:
-                    done, gw = _to_sink_w(w, [x], [gy], True)
-                    if not done:
-                        gw = ReluConvWgrad.apply(x, gy, tuple(w.shape))
-                if ctx.has_bias and ctx.needs_input_grad[2]:
-                    done, gb = _to_sink(ctx.bias, lambda out, acc: channel_sum_raw(gy, out=out, accum=acc))
-                    if not done:
-                        gb = ChannelSum.apply(gy)
-        return gx, gw, gb
-
-
-class ReluConvWgrad(Function):
-    """gw = wgrad(relu(x), gy). Its adjoints: d_x = dgrad(gy, ggw) * [x > 0], d_gy = conv(relu(x), ggw)."""
-
-    @staticmethod
-    def forward(ctx, x, gy, wshape):
-        ctx.save_for_backward(x, gy)
-        return conv_wgrad_raw(x, gy, wshape, relu_in=True)
-
-    @staticmethod
-    def backward(ctx, ggw):
-        x, gy = ctx.saved_tensors
-        d_x = d_gy = None
-        if ctx.needs_input_grad[0]:
-            d_x = ReluMask.apply(ConvDgrad.apply(gy, ggw), x)
-        if ctx.needs_input_grad[1]:
-            d_gy = ReluConv.apply(x, ggw, None)
-        return d_x, d_gy, None
-
-
-class ChannelSum(Function):
-    @staticmethod
-    def forward(ctx, t):
-        ctx.shape = tuple(t.shape)
-        return channel_sum_raw(t)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        shp = ctx.shape
-        rows = shp[0] * shp[1]
-        S = 1
-        for s in shp[2:]:
-            S *= s
-        gg = g.unsqueeze(0).expand(shp[0], shp[1]).contiguous()
-        out = torch.empty(shp, device=g.device, dtype=torch.float32)
-        check(lib().t2v_rowbcast(_p(gg), _p(out), rows, S, _stream()), 't2v_rowbcast')
-        return out
-
-
 def conv(x, w, b=None):
     """Differentiable stride-1 same-padded convolution for [N,C,D,H,W], [N,C,H,W] or [N,C] inputs."""
     dim = x.dim()
-    y = Conv.apply(_as5(x), _as5(w), b)
+    y = ConvG.apply(_as5(w), b, False, _as5(x))[0]
     if dim == 4:
         return y.squeeze(2)
     if dim == 2:
@@ -826,7 +623,7 @@ def conv(x, w, b=None):
 def relu_conv(x, w, b=None):
     """conv(relu(x), w) + b with the ReLU fused into the gather."""
     dim = x.dim()
-    y = ReluConv.apply(_as5(x), _as5(w), b)
+    y = ConvG.apply(_as5(w), b, True, _as5(x))[0]
     return y.squeeze(2) if dim == 4 else y
 
 
@@ -1742,12 +1539,11 @@ class ConvLSTMFn(Function):
                                            B, CS, _stream()), 't2v_lstm_gates_bwd')
             gc = gcp
             if t > 0:
-                gh_next, _ = conv_packed_raw(gpre[t], wph1, 4 * Cc, Cc, k)
+                gh_next = conv_packed_raw(gpre[t], wph1, 4 * Cc, Cc, k)
         gx = None
         if ctx.needs_input_grad[0]:
             wpx1 = packed_fused(wx5, ts, 1)
-            gx, _ = conv_packed_raw(gpre[0], wpx1, 4 * Cc, Cc, k)
-            gx = gx.squeeze(2)
+            gx = conv_packed_raw(gpre[0], wpx1, 4 * Cc, Cc, k).squeeze(2)
         w4shape = (4 * Cc, Cc) + k
         gb4 = channel_sum_raw(gpre.view(steps * B, 4 * Cc, 1, h, w))      # every step contributes to the bias
         gbx = [gb4[g * Cc:(g + 1) * Cc] for g in range(4)]
@@ -1761,11 +1557,11 @@ class ConvLSTMFn(Function):
             gin = gpre[1:].reshape((steps - 1) * B, 4 * Cc, 1, h, w)
             gwh = _fused_gates_to_sink(sink, wh, hin, gin, w4shape)
             return (gx, None) + tuple(gwx) + tuple(gbx) + tuple(gwh)
-        gwx4 = conv_wgrad_raw(x5, gpre[0], w4shape)                       # all four gates at once
+        gwx4 = conv_group_wgrad_raw([x5], [gpre[0]], w4shape)             # all four gates at once
         if steps > 1:
             hin = hs[:steps - 1].reshape((steps - 1) * B, Cc, 1, h, w)    # time folded into the batch
             gin = gpre[1:].reshape((steps - 1) * B, 4 * Cc, 1, h, w)
-            gwh4 = conv_wgrad_raw(hin, gin, w4shape)
+            gwh4 = conv_group_wgrad_raw([hin], [gin], w4shape)
         else:
             gwh4 = _zeros_like(gwx4)
         gwx = [gwx4[g * Cc:(g + 1) * Cc].squeeze(2) for g in range(4)]
@@ -2327,7 +2123,7 @@ def lstm_encode(tokens, lengths, embed_weight, lstm, hidden_size, num_layers, bi
                 sfx = '_l%d%s' % (layer, '_reverse' if d else '')
                 w_ih, w_hh = getattr(lstm, 'weight_ih' + sfx), getattr(lstm, 'weight_hh' + sfx)     # parameters: packed / transposed once
                 bsum = _ew(lib().t2v_add, 't2v_add', getattr(lstm, 'bias_ih' + sfx).detach(), getattr(lstm, 'bias_hh' + sfx).detach())
-                xprojs.append(conv_fwd_raw(_as5(inp), _as5(w_ih), bsum).view(B, L, 4 * H))        # all time steps: one GEMM
+                xprojs.append(conv_group_raw([_as5(inp)], _as5(w_ih), bsum)[0].view(B, L, 4 * H))        # all time steps: one GEMM
                 whts.append(transposed_weight(w_hh))                                              # [H, 4H]: coalesced reads in the step kernel
                 bufss.append([(torch.empty_like(zero), torch.empty_like(zero)) for _ in range(2)])     # ping-pong (h, c)
 
@@ -2668,7 +2464,8 @@ def set_draws(d):
 # ------------------------------------------------------------------------------------------------
 # GROUPED convolutions: the pyramid levels of the multi-scale discriminator share weights, so each layer
 # is ONE launch over all levels (and one weight-gradient launch whose result is already the sum over
-# levels — no per-level accumulation). Closed under differentiation like the single-tensor triple.
+# levels — no per-level accumulation). A single tensor (`conv`, `relu_conv`, `linear`) is a group of one: this is the
+# only convolution triple, closed under differentiation.
 # ------------------------------------------------------------------------------------------------
 
 class _TapSet(object):
@@ -2705,35 +2502,45 @@ def _group_table(ins, outs, geoms, slot_of, masks=None, dstride=0):
     return arr
 
 
-def conv_group_raw(xs5, w5, bias=None, relu_in=False, mode=0, masks=None, outs=None, accum=False, even_frames=False):
-    """mode 0: ys[i] = conv(xs[i], w) (+bias); mode 1: data gradient (xs are dL/dy, channels swap roles).
-    masks: ys[i] is zeroed where masks[i] <= 0 (the ReLU adjoint, fused into the epilogue)."""
-    if len(xs5) > MAX_GROUPS:
-        raise ValueError('at most %d tensors per grouped convolution' % MAX_GROUPS)
-    xs5 = [_c(t) for t in xs5]
-    w5 = _c(w5)
-    Cout_w, Cin_w = w5.shape[0], w5.shape[1]
-    cin, cout = (Cin_w, Cout_w) if mode == 0 else (Cout_w, Cin_w)
-    k = tuple(w5.shape[2:])
-    geoms = [conv_geom(t.shape[0], cin, t.shape[2], t.shape[3], t.shape[4], cout, k[0], k[1], k[2]) for t in xs5]
+def _conv_table(ins, outs, cin, cout, k, masks=None, dstride=0):
+    """(member table, tap set) of one grouped forward / data-gradient launch: the packed weight holds the union of the taps
+    the members need (`_TapSet`), each member's taps point at their slots in it."""
+    geoms = [conv_geom(t.shape[0], cin, t.shape[2], t.shape[3], t.shape[4], cout, k[0], k[1], k[2]) for t in ins]
     mask = 0
     for g in geoms:
         mask |= g.mask
     ts = _tapset(geoms[0].T, mask)
     slot_of = {t: j for j, t in enumerate(ts.taps)}
+    return _group_table(ins, outs, geoms, slot_of, masks, dstride), ts
+
+
+def _fwd_workspace(arr, n, cin, cout, device):
+    """split-K workspace of one grouped forward launch (None when the launch plan does not split)."""
+    nws = int(lib().t2v_conv_fwd_grouped_ws_floats(arr, n, cin, cout))
+    if nws < 0:
+        raise RuntimeError('bad grouped conv geometry')
+    return torch.empty((nws,), device=device, dtype=torch.float32) if nws > 0 else None
+
+
+def conv_group_raw(xs5, w5, bias=None, relu_in=False, mode=0, masks=None, outs=None, accum=False, even_frames=False):
+    """mode 0: ys[i] = conv(xs[i], w) (+bias); mode 1: data gradient (xs are dL/dy, channels swap roles).
+    masks: ys[i] is zeroed where masks[i] <= 0 (the ReLU adjoint, fused into the epilogue)."""
+    if len(xs5) > MAX_GROUPS:
+        raise ValueError('at most %d tensors per grouped convolution' % MAX_GROUPS)
     if even_frames and (mode != 0 or masks is not None or accum or outs is not None):
         raise ValueError('even_frames is a plain forward option')
+    xs5 = [_c(t) for t in xs5]
+    w5 = _c(w5)
+    Cout_w, Cin_w = w5.shape[0], w5.shape[1]
+    cin, cout = (Cin_w, Cout_w) if mode == 0 else (Cout_w, Cin_w)
     ys = outs if outs is not None else [torch.empty((t.shape[0], cout, (t.shape[2] + 1) // 2 if even_frames else t.shape[2]) + tuple(t.shape[3:]),
                                                     device=t.device, dtype=torch.float32) for t in xs5]
     if masks is not None:
         masks = [_c(m) for m in masks]
         if any(m.shape != y.shape for m, y in zip(masks, ys)):
             raise ValueError('mask / output shape mismatch')
-    arr = _group_table(xs5, ys, geoms, slot_of, masks, 2 if even_frames else 0)
-    n = int(lib().t2v_conv_fwd_grouped_ws_floats(arr, len(xs5), cin, cout))
-    if n < 0:
-        raise RuntimeError('bad grouped conv geometry')
-    ws = torch.empty((n,), device=xs5[0].device, dtype=torch.float32) if n > 0 else None
+    arr, ts = _conv_table(xs5, ys, cin, cout, tuple(w5.shape[2:]), masks, 2 if even_frames else 0)
+    ws = _fwd_workspace(arr, len(xs5), cin, cout, xs5[0].device)
     flags = ((FLAG_BIAS if bias is not None else 0) | (FLAG_RELU_IN if relu_in else 0) | (FLAG_MASK_OUT if masks is not None else 0) |
              (FLAG_ACCUM if accum else 0))
     if CONV_PRECISION == 'bf16' and lib().t2v_conv_fwd_grouped_bf16_ok(arr, len(xs5), cin, cout):
@@ -2746,17 +2553,26 @@ def conv_group_raw(xs5, w5, bias=None, relu_in=False, mode=0, masks=None, outs=N
     return ys
 
 
+def _wgrad_table(xs5, gys5, wshape, want_bias, even_frames, sink=None):
+    """(member table, k-split slab) of one grouped weight-gradient launch; the slab comes from `sink`'s workspace when given.
+    even_frames: dL/dy holds the even frames only."""
+    Cout, Cin = wshape[0], wshape[1]
+    k = tuple(wshape[2:])
+    geoms = [conv_geom(t.shape[0], Cin, t.shape[2], t.shape[3], t.shape[4], Cout, k[0], k[1], k[2]) for t in xs5]
+    arr = _group_table(xs5, gys5, geoms, None, None, 2 if even_frames else 0)
+    query = lib().t2v_conv_wgrad_grouped_bias_slab_floats if want_bias else lib().t2v_conv_wgrad_grouped_slab_floats
+    n = int(query(arr, len(xs5), Cin, Cout, k[0], k[1], k[2]))
+    if n <= 0:
+        raise RuntimeError('bad grouped wgrad geometry')
+    slab = sink.alloc_slab(n, xs5[0].device) if sink is not None else torch.empty((n,), device=xs5[0].device, dtype=torch.float32)
+    return arr, slab
+
+
 def conv_group_wgrad_raw(xs5, gys5, wshape, relu_in=False, out=None, accum=False, dbias=None, accum_bias=False, even_frames=False):
     xs5, gys5 = [_c(t) for t in xs5], [_c(t) for t in gys5]
     Cout, Cin = wshape[0], wshape[1]
     k = tuple(wshape[2:])
-    geoms = [conv_geom(t.shape[0], Cin, t.shape[2], t.shape[3], t.shape[4], Cout, k[0], k[1], k[2]) for t in xs5]
-    arr = _group_table(xs5, gys5, geoms, None, None, 2 if even_frames else 0)        # even_frames: dL/dy on the even frames only
-    query = lib().t2v_conv_wgrad_grouped_bias_slab_floats if dbias is not None else lib().t2v_conv_wgrad_grouped_slab_floats
-    n = int(query(arr, len(xs5), Cin, Cout, k[0], k[1], k[2]))
-    if n <= 0:
-        raise RuntimeError('bad grouped wgrad geometry')
-    slab = torch.empty((n,), device=xs5[0].device, dtype=torch.float32)
+    arr, slab = _wgrad_table(xs5, gys5, wshape, dbias is not None, even_frames)
     dw = out if out is not None else torch.empty(tuple(wshape), device=xs5[0].device, dtype=torch.float32)
     flags = (FLAG_RELU_IN if relu_in else 0) | (FLAG_ACCUM if accum else 0) | (FLAG_BF16 if CONV_PRECISION == 'bf16' else 0)
     if dbias is not None:
@@ -2769,23 +2585,12 @@ def conv_group_wgrad_raw(xs5, gys5, wshape, relu_in=False, out=None, accum=False
     return dw
 
 
-def _wgrad_bias_fused(xs5, wshape):
-    """True when the weight-gradient kernel for these members sums dL/dy on the side (all three kernels do)."""
-    return True
-
-
 def _wgrad_partial_launch(xs5, gys5, wshape, relu_in, want_bias, sink=None, even_frames=False):
     """The weight-gradient main kernel alone: returns (WgradSrc describing the k-split partial sums, the slab holding them)."""
     xs5, gys5 = [_c(t) for t in xs5], [_c(t) for t in gys5]
     Cout, Cin = wshape[0], wshape[1]
     k = tuple(wshape[2:])
-    geoms = [conv_geom(t.shape[0], Cin, t.shape[2], t.shape[3], t.shape[4], Cout, k[0], k[1], k[2]) for t in xs5]
-    arr = _group_table(xs5, gys5, geoms, None, None, 2 if even_frames else 0)
-    query = lib().t2v_conv_wgrad_grouped_bias_slab_floats if want_bias else lib().t2v_conv_wgrad_grouped_slab_floats
-    n = int(query(arr, len(xs5), Cin, Cout, k[0], k[1], k[2]))
-    if n <= 0:
-        raise RuntimeError('bad grouped wgrad geometry')
-    slab = sink.alloc_slab(n, xs5[0].device) if sink is not None else torch.empty((n,), device=xs5[0].device, dtype=torch.float32)
+    arr, slab = _wgrad_table(xs5, gys5, wshape, want_bias, even_frames, sink)
     src = WgradSrc()
     flags = (FLAG_RELU_IN if relu_in else 0) | (FLAG_BF16 if CONV_PRECISION == 'bf16' else 0)
     check(lib().t2v_conv_wgrad_grouped_partial(arr, len(xs5), Cin, Cout, k[0], k[1], k[2], _p(slab), 1 if want_bias else 0, flags,
@@ -2906,14 +2711,7 @@ def even_frames_ok(xs, w):
     if len(xs) > MAX_GROUPS or w.dim() != 5 or not xs[0].is_cuda:
         return False
     cout, cin = w.shape[0], w.shape[1]
-    k = tuple(w.shape[2:])
-    geoms = [conv_geom(t.shape[0], cin, t.shape[2], t.shape[3], t.shape[4], cout, k[0], k[1], k[2]) for t in xs]
-    mask = 0
-    for g in geoms:
-        mask |= g.mask
-    ts = _tapset(geoms[0].T, mask)
-    slot_of = {t: j for j, t in enumerate(ts.taps)}
-    arr = _group_table(xs, [None] * len(xs), geoms, slot_of, None, 2)
+    arr, _ = _conv_table(xs, [None] * len(xs), cin, cout, tuple(w.shape[2:]), None, 2)
     out = (C.c_int32 * 8)()
     if lib().t2v_conv_fwd_plan(arr, len(xs), cin, cout, FLAG_RELU_IN, out) != 0 or out[0] != 5 or out[7] != 1:
         return False
@@ -3291,12 +3089,19 @@ class ChannelSumG(Function):
 
     @staticmethod
     def forward(ctx, *gys):
+        ctx.shapes = [tuple(g.shape) for g in gys]
         return channel_sum_group_raw(gys)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        raise RuntimeError('bias gradients are first-order only on this path')
+        outs = []
+        for shp in ctx.shapes:                    # every voxel of every member receives its channel's gradient
+            gg = g.unsqueeze(0).expand(shp[0], shp[1]).contiguous()
+            out = torch.empty(shp, device=g.device, dtype=torch.float32)
+            check(lib().t2v_rowbcast(_p(gg), _p(out), shp[0] * shp[1], out.numel() // (shp[0] * shp[1]), _stream()), 't2v_rowbcast')
+            outs.append(out)
+        return tuple(outs)
 
 
 def conv_group(xs, w, b=None, relu_in=False):
@@ -3338,7 +3143,7 @@ def add_group(as_, bs):
     return list(AddG.apply(*(list(as_) + list(bs))))
 
 
-for _cls in (Conv, ConvDgrad, ConvWgrad, ReluConv, ReluConvWgrad, Relu, ReluMask, Add, AvgPool3d, AddAvgPool3d, AvgPool3dBwd, MaxPool2x2,
+for _cls in (Relu, ReluMask, Add, AvgPool3d, AddAvgPool3d, AvgPool3dBwd, MaxPool2x2,
              MaxScatter, MaxGather, RowSum, RowBcast, Bmm, Softmax, SoftmaxBwd, Dot, ScaleDev, CatFeatures, SliceCols,
              EmbedCols, CatBatch, ConvWgradG):
     _pass_none_through(_cls)

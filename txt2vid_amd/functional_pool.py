@@ -408,7 +408,7 @@ class UpConvFn(Function):
             # as much work as the plain convolution of the up-sampled map, which has no second pass: forward the plain way (the
             # backward below never needs the up-sampled tensor either way)
             TF = _TF()
-            return TF.conv_fwd_raw(TF.Upsample2x.apply(x).unsqueeze(2), w5, b).squeeze(2)
+            return TF.conv_group_raw([TF.Upsample2x.apply(x).unsqueeze(2)], w5, b)[0].squeeze(2)
         planes = pool_dgrad_raw([x.unsqueeze(2)], [(N, cin, 1, 2 * h, 2 * w_)], [0], w5, transpose=True)
         y = unbox_raw(planes, [full], [0], scale=1.0, bias=b)[0]
         return y.squeeze(2)
