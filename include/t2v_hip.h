@@ -543,6 +543,17 @@ int t2v_pool_conv_plan(int what, const t2v_conv_group* groups, int ngroups, int 
 int t2v_synth_clips(const int64_t* index_dev, int B, int64_t seed, int T, int C, int S, const int32_t* vocab_ids, float* vids,
                     int64_t* tokens, int32_t* err_dev, void* stream);
 
+/* ---- input row, real data: batches gathered from an HBM-resident uint8 frame cache -----------------------------------------
+ * Replaces, for a frame-folder dataset (txt2vid/data/__init__.py:201-255, default_transform :357-370), the per-batch host
+ * decode + float conversion + H2D copy: cache_u8 holds n_rows frames of C*H*W bytes (channel-planar, already cropped and
+ * converted by PIL on the host, once), row_index: int64 [B*T] on the device names the cache row of every output frame, lut: 256
+ * floats on the device, lut[u] = the float default_transform yields for byte u (computed on the host with the same expression:
+ * bit-exact by construction). out: float [B,T,C,H,W] = lut[cache_u8[row_index]]. Any C*H*W and any base alignment (rows whose
+ * start is not 16-byte aligned take a scalar head / tail). A row index outside [0, n_rows) is never dereferenced: it is clamped
+ * and err_dev (optional int32 on the device, zeroed by the caller) is set to 1. */
+int t2v_clip_gather(const uint8_t* cache_u8, int64_t n_rows, const int64_t* row_index, int B, int T, int C, int H, int W,
+                    const float* lut, float* out, int32_t* err_dev, void* stream);
+
 /* ---- optional launch instrumentation for bench.py's roofline line -----------------------------------
  * Between begin and end every conv-GEMM launch is bracketed by a hipEvent pair recorded on the launch
  * stream. end() synchronises and fills out[kind*3+{0,1,2}] = {total ms, executed flops, launches};

@@ -131,6 +131,56 @@ __global__ __launch_bounds__(256) void synth_clips_k(const int64_t* __restrict__
     }
 }
 
+// Real-data twin of synth_clips_k: batch rows gathered from an HBM-resident uint8 frame cache (one [C,H,W] row of N bytes per
+// decoded frame, rows back to back) and converted through a 256-entry table the host computed with default_transform's own
+// float32 expression, so out == the host item bit for bit. One lane per 16 source bytes: a 16-byte load, 16 LDS look-ups, four
+// 16-byte stores. A row of the cache starts at base + row * N, which is 16-byte aligned only when N is: unit 0 of a row is its
+// scalar head (the bytes in front of the first aligned address), units 1..nbody the aligned body, the next one the scalar tail.
+// Streaming, HBM bound: 1 byte read + 4 bytes written per sample.
+__global__ __launch_bounds__(256) void clip_gather_k(const uint8_t* __restrict__ cache, int64_t n_rows, const int64_t* __restrict__ row_index,
+                                                     int64_t n_slots, int64_t N, int upr, const float* __restrict__ lut,
+                                                     float* __restrict__ out, int32_t* __restrict__ err) {
+    __shared__ float s_lut[256];
+    s_lut[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t slot = u / upr;
+    if (slot >= n_slots) return;
+    const int c = (int)(u - slot * upr);
+    int64_t row = row_index[slot];
+    if (row < 0 || row >= n_rows) {                   // never dereferenced: clamped and flagged (the loader raises at its next check)
+        row = row < 0 ? 0 : n_rows - 1;
+        if (c == 0 && err) *err = 1;
+    }
+    const uint8_t* src = cache + row * N;
+    float* dst = out + slot * N;
+    int64_t head = (int64_t)((16u - (unsigned)((uintptr_t)src & 15u)) & 15u);
+    if (head > N) head = N;
+    const int64_t nbody = (N - head) / 16;
+    if (c >= 1 && c <= nbody) {
+        const int64_t off = head + (int64_t)(c - 1) * 16;
+        const uint4 q = *reinterpret_cast<const uint4*>(src + off);
+        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+        float v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = s_lut[(w[j >> 2] >> (8 * (j & 3))) & 0xffu];
+        float* o = dst + off;
+        if (((uintptr_t)o & 15u) == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) reinterpret_cast<float4*>(o)[j] = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+        } else {                                      // (N not a multiple of 4: the output row is not float4 aligned)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) o[j] = v[j];
+        }
+        return;
+    }
+    int64_t lo, hi;
+    if (c == 0) { lo = 0; hi = head; }
+    else if (c == nbody + 1) { lo = head + nbody * 16; hi = N; }
+    else return;
+    for (int64_t e = lo; e < hi; ++e) dst[e] = s_lut[src[e]];
+}
+
 }  // namespace
 
 extern "C" int t2v_synth_clips(const int64_t* index_dev, int B, int64_t seed, int T, int C, int S, const int32_t* vocab_ids, float* vids,
@@ -141,5 +191,19 @@ extern "C" int t2v_synth_clips(const int64_t* index_dev, int B, int64_t seed, in
     for (int i = 0; i < T2V_SYNTH_VOCAB; ++i) voc.id[i] = vocab_ids[i];
     (void)hipGetLastError();
     hipLaunchKernelGGL(synth_clips_k, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, index_dev, seed, T, C, S, voc, vids, tokens, err_dev);
+    return hipGetLastError() == hipSuccess ? T2V_OK : T2V_ELAUNCH;
+}
+
+extern "C" int t2v_clip_gather(const uint8_t* cache_u8, int64_t n_rows, const int64_t* row_index, int B, int T, int C, int H, int W,
+                               const float* lut, float* out, int32_t* err_dev, void* stream) {
+    if (!cache_u8 || !row_index || !lut || !out || n_rows < 1 || B < 1 || T < 1 || C < 1 || H < 1 || W < 1) return T2V_EINVAL;
+    const int64_t N = (int64_t)C * H * W, n_slots = (int64_t)B * T;
+    if (N >= (1LL << 30) || n_slots * N >= (1LL << 40) || n_rows >= (1LL << 40) / N) return T2V_EINVAL;
+    const int upr = (int)(N / 16) + 2;                // units per row: head + aligned 16-byte chunks + tail
+    const int64_t blocks = (n_slots * upr + 255) / 256;
+    if (blocks >= (1LL << 31)) return T2V_EINVAL;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(clip_gather_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, cache_u8, n_rows, row_index, n_slots, N, upr,
+                       lut, out, err_dev);
     return hipGetLastError() == hipSuccess ? T2V_OK : T2V_ELAUNCH;
 }

@@ -1,7 +1,8 @@
 """Input side of the hot path: the batch *contract* of txt2vid/data/__init__.py (`Dataset` :158-258,
 `Vocab` :260-316, `collate_fn` :326-355, `default_transform` :357-370, `my_dataset` :376-377): the
 frame-folder reader (PIL only: no cv2 / DALI / torchvision / lmdb), synthetic Moving-MNIST-shaped clips for
-machines without a dataset, and the pinned-memory prefetcher that replaces `data_prefetcher` (:131-156).
+machines without a dataset, the pinned-memory prefetcher that replaces `data_prefetcher` (:131-156), and (frames.py) the
+HBM-resident uint8 frame cache that serves a frame folder's batches with one gather launch.
 
 A batch is (videos [B,T,C,H,W] float32 in [-1,1], tokens [B,L] int64 zero-padded, lengths list desc).
 """
@@ -84,22 +85,33 @@ def pick_frames(frame_ids, num_frames=16, random=False, rng=None):
     return [frame_ids[i] for i in keep]
 
 
+def unit_range(u8):
+    """uint8 -> float32 in [-1,1]: /255, (x-0.5)/0.5 (ToTensor + Normalize(0.5, 0.5)). The ONE expression behind both the host
+    transform and the frame cache's 256-entry table (`FrameCache.lut`), so the two agree bit for bit by construction."""
+    a = np.asarray(u8, dtype=np.float32) / 255.0
+    return (a - 0.5) / 0.5
+
+
 def default_transform(frame_size=None, num_channels=3):
     """PIL image -> float32 [C,h,w] in [-1,1]: centre crop, (grey), /255, (x-0.5)/0.5 — the torchvision
-    pipeline of data/__init__.py:357-370 without torchvision (absent here)."""
+    pipeline of data/__init__.py:357-370 without torchvision (absent here). The closure carries `crop` (h, w), `num_channels`
+    and `integer_part` (crop + convert, PIL -> PIL): what the HBM frame cache stores is that part's bytes."""
     fs = list(frame_size) if isinstance(frame_size, (list, tuple)) else [frame_size]
     if len(fs) == 1:
         fs.append(fs[0])
     ch, cw = int(fs[0]), int(fs[1])
 
-    def transform(img):
+    def integer_part(img):
         w, h = img.size
         left, top = int(round((w - cw) / 2.0)), int(round((h - ch) / 2.0))
         img = img.crop((left, top, left + cw, top + ch))            # PIL zero-fills outside, like CenterCrop's pad
-        img = img.convert('RGB' if num_channels == 3 else 'L')
-        a = np.asarray(img, dtype=np.float32) / 255.0
+        return img.convert('RGB' if num_channels == 3 else 'L')
+
+    def transform(img):
+        a = unit_range(integer_part(img))
         a = a[None] if a.ndim == 2 else a.transpose(2, 0, 1)
-        return torch.from_numpy(np.ascontiguousarray((a - 0.5) / 0.5))
+        return torch.from_numpy(np.ascontiguousarray(a))
+    transform.integer_part, transform.crop, transform.num_channels = integer_part, (ch, cw), int(num_channels)
     return transform
 
 
@@ -129,15 +141,28 @@ class Dataset(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.captions)
 
+    def frame_files(self, video_id):
+        """The numbered frames of one video folder, numerically sorted: [(n, file name), ...]."""
+        import os
+        ext = {}
+        for name in os.listdir(os.path.join(self.video_dir, str(video_id))):
+            stem, suffix = os.path.splitext(name)
+            if suffix in ('.jpg', '.png') and stem.isdigit():
+                ext[int(stem)] = name
+        return [(n, ext[n]) for n in sorted(ext)]
+
+    def tokens(self, idx):
+        """Token ids of item `idx`'s caption (<start> ... <end>)."""
+        toks = [self.vocab(t) for t in self.vocab.tokenize(self.captions[idx])]
+        if toks[-1] != self.vocab(self.vocab.END):
+            toks.append(self.vocab(self.vocab.END))
+        return toks
+
     def __getitem__(self, idx):
         import os
         from PIL import Image
         folder = os.path.join(self.video_dir, str(self.video_ids[idx]))
-        ext = {}
-        for name in os.listdir(folder):
-            stem, suffix = os.path.splitext(name)
-            if suffix in ('.jpg', '.png') and stem.isdigit():
-                ext[int(stem)] = name
+        ext = dict(self.frame_files(self.video_ids[idx]))
         ids = sorted(ext)
         n = self.random_frames if self.random_frames else self.num_frames
         picked = pick_frames(ids, num_frames=n, random=bool(self.random_frames))
@@ -147,10 +172,7 @@ class Dataset(torch.utils.data.Dataset):
                 img.load()
                 frames.append(self.transform(img) if self.transform else img)
         frames = torch.stack(frames)
-        toks = [self.vocab(t) for t in self.vocab.tokenize(self.captions[idx])]
-        if toks[-1] != self.vocab(self.vocab.END):
-            toks.append(self.vocab(self.vocab.END))
-        return frames, torch.tensor(toks, dtype=torch.float32)
+        return frames, torch.tensor(self.tokens(idx), dtype=torch.float32)
 
 
 class SyntheticMovingDigits(torch.utils.data.Dataset):
@@ -273,34 +295,40 @@ def collate_fn(data):
 
 
 def my_dataset(data=None, vocab=None, anno=None, transform=None, random_frames=False, num_frames=16, use_lmdb=False,
-               **synthetic_args):
+               on_device=False, cache_file=None, **synthetic_args):
     """Factory named by config/*.json (`"class": "txt2vid.data.my_dataset"`, data/__init__.py:376-377): a
     frame-folder `Dataset` when `data` is a directory (captions pickle = `--anno`); `data="synthetic"` (or a
     path that does not exist, e.g. the reference's own config/synth.json on a machine without the files)
-    yields the synthetic clips, with `size= channels= length= seed=` forwarded."""
+    yields the synthetic clips, with `size= channels= length= seed=` forwarded. `on_device` (and, for a frame folder, `cache_file`)
+    is recorded on the dataset: `get_loader(..., device=cuda)` then serves the batches from HBM."""
     import os
     if data is not None and data != 'synthetic' and os.path.isdir(str(data)):
         if anno is None:
             raise ValueError('a frame-folder dataset needs the captions pickle (--anno)')
         if transform is None:
             transform = default_transform([synthetic_args.get('size', 64)], synthetic_args.get('channels', 3))
-        return Dataset(video_dir=data, vocab=vocab, captions=anno, transform=transform, random_frames=random_frames,
+        dset = Dataset(video_dir=data, vocab=vocab, captions=anno, transform=transform, random_frames=random_frames,
                        num_frames=num_frames, use_lmdb=use_lmdb)
-    return SyntheticMovingDigits(num_frames=num_frames, vocab=vocab, **synthetic_args)
+        dset.on_device, dset.cache_file = bool(on_device), cache_file
+        return dset
+    return SyntheticMovingDigits(num_frames=num_frames, vocab=vocab, on_device=on_device, **synthetic_args)
 
 
 def get_loader(dset=None, batch_size=64, val=False, num_workers=0, has_captions=True, rank=0, world=1, seed=0, device=None):
     """data/__init__.py:379-383. With `world` > 1 every rank reads its own 1/world of each epoch's
     permutation (one process per GPU; the reference's single-process DataParallel split one big batch).
     Synthetic clips with `on_device` set (config: `"args": {"data": "synthetic", "on_device": true}`) and a CUDA `device` are
-    generated in HBM by `DeviceSyntheticLoader` instead of on host workers."""
-    if isinstance(dset, SyntheticMovingDigits) and getattr(dset, 'on_device', False) and device is not None and \
-            torch.device(device).type == 'cuda':
+    generated in HBM by `DeviceSyntheticLoader` instead of on host workers; a frame folder with `on_device` set is decoded once
+    into an HBM-resident uint8 cache and served by `DeviceFrameLoader` (`num_workers` is not used on that path)."""
+    on_cuda = device is not None and torch.device(device).type == 'cuda'
+    if isinstance(dset, SyntheticMovingDigits) and getattr(dset, 'on_device', False) and on_cuda:
         return DeviceSyntheticLoader(dset, batch_size, device, shuffle=not val)
     sampler = None
     if world > 1 and not isinstance(dset, SyntheticMovingDigits):     # synthetic clips already differ per rank (seed+rank)
         sampler = torch.utils.data.distributed.DistributedSampler(dset, num_replicas=world, rank=rank, shuffle=not val,
                                                                   seed=int(seed), drop_last=True)
+    if isinstance(dset, Dataset) and getattr(dset, 'on_device', False) and on_cuda:
+        return DeviceFrameLoader(dset, frame_cache_for(dset), batch_size, device, shuffle=not val, sampler=sampler)
     return torch.utils.data.DataLoader(dset, batch_size=batch_size, shuffle=(not val) and sampler is None, sampler=sampler,
                                        num_workers=num_workers, collate_fn=collate_fn, drop_last=True, pin_memory=True)
 
@@ -339,3 +367,6 @@ class DevicePrefetcher(object):
         x, y = self.nx, self.ny
         self._preload()
         return x, y
+
+
+from .frames import FrameCache, DeviceFrameLoader, clip_gather, frame_cache_for  # noqa: E402  (needs the names above)
