@@ -446,6 +446,19 @@ int t2v_adam_multi(const t2v_adam_job* jobs, int njobs, float lr, float b1, floa
 int t2v_sgd_multi(const t2v_adam_job* jobs, int njobs, float lr, float momentum, float gscale, int first_step, void* stream);
 int t2v_adam_tick(float* state, float b1, float b2, void* stream);
 
+/* ---- weight average (opt-in EMA of the generator; not in the reference) ------------- */
+/* Multi-tensor like t2v_adam_multi: `jobs` is a HOST array of (average, parameter, element count) with device pointers
+   inside, 64 per launch. Per element e = d*e + (1-d)*p, where d = decay once the update count t > start and d = 0 (a plain
+   copy of the weights) before. t = count_dev[0] when count_dev != NULL (device-resident, for HIP-graph replay), else
+   count_host. T2V_EINVAL on NULL pointers, n < 1 or n > INT_MAX. */
+typedef struct t2v_ema_job { void* e; void* p; int64_t n; } t2v_ema_job;
+int t2v_ema_multi(const t2v_ema_job* jobs, int njobs, float decay, float start, const float* count_dev, float count_host,
+                  void* stream);
+/* count[0] += 1: advances the device-resident update count (one thread; the t2v_adam_tick pattern). */
+int t2v_ema_tick(float* count, void* stream);
+/* Exchanges the contents of e and p of every job in place (the addresses stay the same). */
+int t2v_swap_multi(const t2v_ema_job* jobs, int njobs, void* stream);
+
 /* ---- pyramid (trainer.py:131-165, layers.py:106-111) ------------------------------------------- */
 /* y[b,c,t,h,w] = x[b*sb, c, t*st+bt, (h*H)/Ho, (w*W)/Wo]  — Subsample + nearest F.interpolate. */
 int t2v_pyramid_gather(const float* x, float* y, int B, int C, int T, int H, int W, int Bo, int To, int Ho, int Wo,

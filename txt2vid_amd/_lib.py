@@ -33,6 +33,11 @@ class AdamJob(C.Structure):
     _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('n', C.c_int64)]
 
 
+class EmaJob(C.Structure):
+    """t2v_ema_job (include/t2v_hip.h)."""
+    _fields_ = [('e', C.c_void_p), ('p', C.c_void_p), ('n', C.c_int64)]
+
+
 class PoolJob(C.Structure):
     """t2v_pool_job (include/t2v_hip.h)."""
     _fields_ = [('x', C.c_void_p), ('x2', C.c_void_p), ('y', C.c_void_p), ('add', C.c_void_p), ('NC', C.c_int32), ('D', C.c_int32), ('H', C.c_int32),
@@ -187,6 +192,9 @@ SIGNATURES = {
     't2v_adam_multi': [_P, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P],
     't2v_sgd_multi': [_P, _I, _F, _F, _F, _I, _P],
     't2v_adam_tick': [_P, _F, _F, _P],
+    't2v_ema_multi': [_P, _I, _F, _F, _P, _F, _P],
+    't2v_ema_tick': [_P, _P],
+    't2v_swap_multi': [_P, _I, _P],
     't2v_pyramid_gather': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     't2v_copy2d': [_P, _L, _P, _L, _L, _L, _P],
     't2v_cast_bf16': [_P, _P, _L, _I, _P],

@@ -2607,6 +2607,104 @@ extern "C" int t2v_adam_tick(float* state, float b1, float b2, void* st) {
     return launch_status();
 }
 
+// ---------------------------------------------------------------- weight average (EMA of the generator; not in the reference)
+// Multi-tensor like adam_multi_k: 64 (average, parameter) pairs per launch, pointers by value, 4096-element chunks found by
+// binary search over begin[], float4 body when both pointers are 16-byte aligned. 12 B / element, no reuse: pure streaming.
+struct EmaBatch {
+    float* e[ADAM_MT]; float* p[ADAM_MT];
+    int n[ADAM_MT]; int begin[ADAM_MT + 1]; int njobs;
+};
+static_assert(sizeof(EmaBatch) < 4096 - 64, "EmaBatch travels by value in the kernel arguments (4 KB limit)");
+// e = d e + (1 - d) p with d = decay once the update count exceeds `start`, else 0 (the average copies the weights)
+__global__ __launch_bounds__(256) void ema_multi_k(EmaBatch tb, float decay, float start, const float* count_dev, float count) {
+    if (count_dev) count = count_dev[0];               // device-resident update count (HIP-graph replay)
+    const float d = count > start ? decay : 0.f;
+    const float om = 1.f - d;
+    int lo = 0, hi = tb.njobs;                         // largest j with begin[j] <= blockIdx.x
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tb.begin[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
+    const int j = lo;
+    const long base = (long)((int)blockIdx.x - tb.begin[j]) * ADAM_CHUNK;
+    const int len = (int)min((long)ADAM_CHUNK, (long)tb.n[j] - base);
+    float* __restrict__ e = tb.e[j] + base;
+    const float* __restrict__ p = tb.p[j] + base;
+    const bool vec = ((((uintptr_t)e | (uintptr_t)p) & 15) == 0);
+    const int nv = vec ? (len >> 2) : 0;
+    for (int q = threadIdx.x; q < nv; q += 256) {
+        float4 E = ((float4*)e)[q];
+        const float4 P = ((const float4*)p)[q];
+        E.x = d * E.x + om * P.x; E.y = d * E.y + om * P.y; E.z = d * E.z + om * P.z; E.w = d * E.w + om * P.w;
+        ((float4*)e)[q] = E;
+    }
+    for (int i = nv * 4 + threadIdx.x; i < len; i += 256) e[i] = d * e[i] + om * p[i];
+}
+// e <-> p in place (the addresses stay: graph replay and the packed-weight cache keep theirs)
+__global__ __launch_bounds__(256) void swap_multi_k(EmaBatch tb) {
+    int lo = 0, hi = tb.njobs;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tb.begin[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
+    const int j = lo;
+    const long base = (long)((int)blockIdx.x - tb.begin[j]) * ADAM_CHUNK;
+    const int len = (int)min((long)ADAM_CHUNK, (long)tb.n[j] - base);
+    float* __restrict__ e = tb.e[j] + base;
+    float* __restrict__ p = tb.p[j] + base;
+    const bool vec = ((((uintptr_t)e | (uintptr_t)p) & 15) == 0);
+    const int nv = vec ? (len >> 2) : 0;
+    for (int q = threadIdx.x; q < nv; q += 256) {
+        const float4 E = ((float4*)e)[q], P = ((float4*)p)[q];
+        ((float4*)e)[q] = P; ((float4*)p)[q] = E;
+    }
+    for (int i = nv * 4 + threadIdx.x; i < len; i += 256) { const float a = e[i], b = p[i]; e[i] = b; p[i] = a; }
+}
+static int ema_jobs_ok(const t2v_ema_job* jobs, int njobs) {
+    if (!jobs || njobs < 1) return 0;
+    for (int i = 0; i < njobs; ++i)
+        if (!jobs[i].e || !jobs[i].p || jobs[i].n < 1 || jobs[i].n > 0x7fffffffL) return 0;
+    return 1;
+}
+// fills `tb` with jobs[at, at + cnt); returns the block count (one block per 4096-element chunk)
+static long ema_batch(EmaBatch& tb, const t2v_ema_job* jobs, int at, int cnt) {
+    long blocks = 0;
+    for (int i = 0; i < ADAM_MT; ++i) {
+        if (i < cnt) {
+            const t2v_ema_job& jb = jobs[at + i];
+            tb.e[i] = (float*)jb.e; tb.p[i] = (float*)jb.p; tb.n[i] = (int)jb.n; tb.begin[i] = (int)blocks;
+            blocks += (jb.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        } else { tb.e[i] = nullptr; tb.p[i] = nullptr; tb.n[i] = 0; tb.begin[i] = (int)blocks; }
+    }
+    tb.begin[ADAM_MT] = (int)blocks;
+    tb.njobs = cnt;
+    return blocks;
+}
+extern "C" int t2v_ema_multi(const t2v_ema_job* jobs, int njobs, float decay, float start, const float* count_dev, float count_host,
+                             void* st) {
+    if (!ema_jobs_ok(jobs, njobs)) return T2V_EINVAL;
+    for (int at = 0; at < njobs; at += ADAM_MT) {
+        EmaBatch tb;
+        const long blocks = ema_batch(tb, jobs, at, njobs - at < ADAM_MT ? njobs - at : ADAM_MT);
+        if (blocks > 0x7fffffffL) return T2V_EINVAL;
+        T2V_LAUNCH(ema_multi_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, decay, start, count_dev, count_host);
+    }
+    return launch_status();
+}
+extern "C" int t2v_swap_multi(const t2v_ema_job* jobs, int njobs, void* st) {
+    if (!ema_jobs_ok(jobs, njobs)) return T2V_EINVAL;
+    for (int at = 0; at < njobs; at += ADAM_MT) {
+        EmaBatch tb;
+        const long blocks = ema_batch(tb, jobs, at, njobs - at < ADAM_MT ? njobs - at : ADAM_MT);
+        if (blocks > 0x7fffffffL) return T2V_EINVAL;
+        T2V_LAUNCH(swap_multi_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
+    }
+    return launch_status();
+}
+// the device-resident update count the gate of ema_multi_k reads: count += 1 (exact in fp32 up to 2^24 updates)
+__global__ void ema_tick_k(float* count) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) count[0] = count[0] + 1.f;
+}
+extern "C" int t2v_ema_tick(float* count, void* st) {
+    if (!count) return T2V_EINVAL;
+    T2V_LAUNCH(ema_tick_k, dim3(1), dim3(64), 0, S_(st), count);
+    return launch_status();
+}
+
 // ---------------------------------------------------------------- pyramid gather
 __global__ void pyramid_gather_k(const float* x, float* y, int B, int C, int T, int H, int W, int Bo, int To, int Ho, int Wo,
                                  int sb, int stt, int bt, const int32_t* bt_dev) {

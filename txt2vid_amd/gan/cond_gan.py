@@ -23,7 +23,7 @@ def _mean_over_levels(loss, fakes, reals):
 
 class CondGan(object):
     def __init__(self, gen=None, discrims=None, cond_encoder=None, discrim_names=None, sample_mapping=None,
-                 discrim_lambdas=None, gp_scale=1.0):
+                 discrim_lambdas=None, gp_scale=1.0, gen_ema=None):
         assert gen is not None
         assert discrims is not None and len(discrims) >= 1
         if discrim_names is None:
@@ -36,6 +36,7 @@ class CondGan(object):
         self.discrim_names = discrim_names
         self.discrim_lambdas = discrim_lambdas
         self.gp_scale = gp_scale          # data-parallel: world_size, else 1
+        self.gen_ema = gen_ema            # gan.ema.GenAverage of `gen` (--G_ema, not in the reference), or None
 
     def _discrim_weighted_sum(self, losses, kl=None, kl_coeff=0.0):
         """cond_gan.py:26-31: mean over discriminators, or lambda-weighted sum. `kl`: the generator's conditioning-augmentation
@@ -263,6 +264,10 @@ class CondGan(object):
             res['cond'] = self.cond_encoder.state_dict()
         for name, d in zip(self.discrim_names, self.discrims):
             res[name] = d.state_dict()
+        if self.gen_ema is not None:
+            # extra keys next to the reference's layout (its loader reads named keys only): the averaged parameters by name
+            res['gen_ema'] = self.gen_ema.state_dict()
+            res['gen_ema_updates'] = self.gen_ema.updates
         return res
 
     def load_from_dict(self, to_load):
@@ -274,6 +279,10 @@ class CondGan(object):
         for name, d in zip(self.discrim_names, self.discrims):
             if name in to_load:
                 d.load_state_dict(_match_keys(to_load[name], d.state_dict().keys()))
+        if self.gen_ema is not None:
+            # a file without the key (written without --G_ema, or by the reference) leaves the average a copy of the loaded `gen`;
+            # a file with the key loaded into a run without an average ignores it
+            self.gen_ema.load_state_dict(to_load.get('gen_ema'), to_load.get('gen_ema_updates', 0))
 
 
 def _can_batch(real, fake):

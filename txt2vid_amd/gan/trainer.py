@@ -8,6 +8,7 @@ gen_perm (numpy), 4x GP alpha (losses.py:140-145), gen_perm for real_pred (train
 --discrim_steps N / --gen_steps M schedule (trainer.py:228-263): gen_perm + 4x alpha once per D step, then
 gen_perm for real_pred, then 3x Subsample per later G forward (DESIGN "D:G step schedule").
 """
+import argparse
 import os
 import sys
 
@@ -20,8 +21,16 @@ from ..util.metrics import RollingAvg
 from ..util.stopwatch import Stopwatch
 
 
+def _ema_decay(text):
+    v = float(text)
+    if not 0.0 <= v < 1.0:
+        raise argparse.ArgumentTypeError('--G_ema takes a decay in [0, 1) (0 = off), got %r' % text)
+    return v
+
+
 def add_params_to_parser(parser):
-    """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*)."""
+    """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema and
+    --G_ema_start are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
     parser.add_argument('--log_period', type=int, default=20)
@@ -41,6 +50,10 @@ def add_params_to_parser(parser):
     parser.add_argument('--out', type=str, default='out')
     parser.add_argument('--out_samples', type=str, default='out_samples')
     parser.add_argument('--subsample_input', action='store_true', default=False)
+    parser.add_argument('--G_ema', type=_ema_decay, default=0.0,
+                        help='(new) decay of a moving average of the generator weights, used for samples and saved as gen_ema; 0 = off')
+    parser.add_argument('--G_ema_start', type=int, default=0,
+                        help='(new) the average copies the weights for the first N generator updates')
     return parser
 
 
@@ -207,7 +220,7 @@ class TrainStep(object):
         """G part j >= 1: G's update from step j - 1, a new train-mode G forward of the same z (new Subsample phases, BatchNorm
         buffers updated again) and G step j against the same real_pred. D is unchanged since G part 0, so the fused pass
         recomputes the same real_pred; it draws no caption permutation (the reference draws that one once, trainer.py:247)."""
-        self.optG.step()
+        self._g_update()
         self._arm_sink()
         self.fake = self._forward_g()
         if self._fused:
@@ -232,8 +245,16 @@ class TrainStep(object):
         if last:
             self._real_pred = None
 
-    def part_end(self):
+    def _g_update(self):
+        """G's optimiser step and, when the generator's weights are averaged (--G_ema), the average's update right behind it
+        (one tick + one launch per 64 tensors, inside whatever captures this part; nothing without an average)."""
         self.optG.step()
+        ema = getattr(self.gan, 'gen_ema', None)
+        if ema is not None:
+            ema.update()
+
+    def part_end(self):
+        self._g_update()
 
     @property
     def n_parts(self):
@@ -471,7 +492,13 @@ def test(gan=None, num_samples=1, dataset=None, device=None, params=None, channe
             if gan.cond_encoder is not None and len(y) >= 2:
                 _, _, cond = gan.cond_encoder.encode(y[0], y[1])
             z = torch.randn(x.size(0), gan.gen.latent_size).to(device)
-            fake = gan(z, cond=cond)
+            ema = getattr(gan, 'gen_ema', None)
+            if ema is not None:
+                status('sampling from the averaged generator (%d updates)' % ema.updates)
+                with ema.swapped():
+                    fake = gan(z, cond=cond)
+            else:
+                fake = gan(z, cond=cond)
             save_frames(x, '%s/real_%d.png' % (params.out_samples, i), is_images=getattr(params, 'img_model', False))
             if cond is not None and vocab is not None:
                 save_sentences(y[0], path='%s/sentences_%d_%d.txt' % (params.out_samples, i, j), vocab=vocab)
@@ -481,6 +508,20 @@ def test(gan=None, num_samples=1, dataset=None, device=None, params=None, channe
                 status('saving to %s' % path)
                 save_frames(f, path, is_images=getattr(params, 'img_model', False))
     gan.gen.train()
+
+
+def _averaged_samples(gan, z, cond):
+    """The iteration's z (and sentence codes) through the AVERAGED generator, every level rendered: one extra eval-mode forward
+    outside the captured graph (a train-mode one would update the BatchNorm buffers a second time), only on iterations that
+    write a grid. Eval mode renders full clips at every level (no sub-sampling)."""
+    gen = gan.gen
+    was_training = gen.training
+    gen.eval()
+    try:
+        with torch.no_grad(), gan.gen_ema.swapped():
+            return gan(z.detach(), cond=None if cond is None else cond.detach(), output_blocks=range(len(gen.render_blocks)))
+    finally:
+        gen.train(was_training)
 
 
 def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=None, params=None, vocab=None, losses=None,
@@ -601,6 +642,11 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 from .samples import save_frames, save_sentences
                 status('saving to %s (iteration %d)' % (params.out_samples, iteration))
                 save_frames(xs[0], '%s/real_samples.png' % params.out_samples)
+                if getattr(gan, 'gen_ema', None) is not None:
+                    step = graphed.ts if use_graph else ts
+                    fake = _averaged_samples(gan, step._z, None if step.conds is None else step.conds[0])
+                    status('fake samples of iteration %d come from the averaged generator (%d updates)' % (iteration,
+                                                                                                        gan.gen_ema.updates))
                 for f in fake:
                     h, w = f.size(3), f.size(4)
                     save_frames(f.detach(), '%s/fake_samples_epoch_%03d_iter_%06d_%dx%d.png' % (params.out_samples, epoch,

@@ -88,7 +88,7 @@ def main(args):
     else:
         optD = Adam(D_params, lr=args.D_lr, betas=(args.D_beta1, args.D_beta2))
         optG = Adam(G_params, lr=args.G_lr, betas=(args.G_beta1, args.G_beta2))
-    resumed_rng, resumed_iter = None, 0
+    resumed_rng, resumed_iter, resumed_ema = None, 0, None
     gan = CondGan(gen=gen, discrims=discrims, cond_encoder=txt_encoder, discrim_names=args.D_names,
                   discrim_lambdas=args.D_lambdas, gp_scale=float(world))
     if args.weights is not None:
@@ -99,6 +99,8 @@ def main(args):
         if 'optG' in to_load:
             optG.load_state_dict(to_load['optG'])
         resumed_rng, resumed_iter = to_load.get('rng_state'), int(to_load.get('iteration', 0))
+        if 'gen_ema' in to_load and args.G_ema > 0:
+            resumed_ema = (to_load['gen_ema'], to_load.get('gen_ema_updates', 0))
         del to_load
     if world > 1:
         # replicas bit-identical before the first step (whatever each rank's init / checkpoint read produced), then per-rank
@@ -110,6 +112,15 @@ def main(args):
         import numpy as np
         for seeder in (random.seed, np.random.seed, torch.manual_seed):
             seeder(seed + rank + 1000003 * resumed_iter)     # (a resumed run does not replay the first run's draws)
+    if args.G_ema > 0:
+        # moving average of the generator's weights (not in the reference): built from the loaded / initialised and synchronised
+        # weights; every rank then applies the same update to identical replicas, so the averages need no exchange
+        from ..gan.ema import GenAverage
+        gan.gen_ema = GenAverage(gen, args.G_ema, start=args.G_ema_start)
+        if resumed_ema is not None:
+            gan.gen_ema.load_state_dict(*resumed_ema)
+        status('Averaged generator: decay %g after %d updates (%d updates so far)' % (args.G_ema, args.G_ema_start,
+                                                                                     gan.gen_ema.updates))
     if resumed_rng is not None and rank == 0:
         # checkpoints written by this build carry the writer's (rank 0's) generator states: the resumed run continues the draw
         # sequence where the saved one stopped (reference-written files have no such key and start from --seed)
