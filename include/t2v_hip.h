@@ -619,6 +619,36 @@ int t2v_ca_fwd(const float* h, const float* z, const float* eps, float* out, flo
 int t2v_ca_bwd(const float* gout, const float* gkl, float kl_coeff, const float* h, const float* eps, float* gh, int B, int L, int D,
                void* stream);
 
+/* ---- differentiable augmentation of the discriminator's inputs (DiffAugment; opt-in, --D_aug; not in the reference) ----------
+ * One launch transforms up to T2V_MAX_GROUPS member tensors (the real and the generated pyramid of one step). Member clips are
+ * [N, C, T, S, S] (square frames); clip j reads row j * row_stride of its parameter block u [rows, T2V_AUG_K] of uniforms in
+ * [0, 1): columns 0-2 brightness / saturation / contrast, 3-4 the shift (tx, ty), 5-6 the cutout centre (cx, cy), 7 unused.
+ * With b = u0 - 0.5, s = 2 u1, c = u2 + 0.5, m = the voxel's mean over channels and mu = mean(clip) + b:
+ *   color:       v = ((x - m) s + m + b - mu) c + mu
+ *   translation: r = (S + 4) / 8, tx = min(floor(u3 (2r + 1)), 2r) - r (ty from u4; the product is exact, taken in double);
+ *                out(h, w) = v(h - ty, w - tx), 0 outside the frame
+ *   cutout:      size = (S + 1) / 2, n = S + 1 - size % 2, cx = min(floor(u5 n), n - 1) (cy from u6);
+ *                out = 0 for columns in [cx - size / 2, cx - size / 2 + size) and rows in the same range around cy
+ * policy: T2V_AUG_* bits, applied in that order. The clip sum and the apply step share the launch: a clip is split over up to
+ * 16 workgroups, each of which re-reads the whole clip for the sum in the same order (bit-identical mu in all of them), so
+ * there is no workspace and no second launch at any size.
+ * t2v_diffaug_fwd: y = T(x). t2v_diffaug_bwd: x holds dL/dy, y receives dL/dx = T^T(dL/dy) (T is affine per clip: mask and
+ * shift back, then c g + (1 - c) mean_clip(g), then s g + (1 - s) mean_channels(g)). fp32, x != y.
+ * T2V_EINVAL on n outside 1..T2V_MAX_GROUPS, null pointers, empty extents, policy 0 or unknown policy bits, row_stride < 1, or a
+ * parameter block with fewer than (N - 1) * row_stride + 1 rows. */
+#define T2V_AUG_K 8
+enum { T2V_AUG_COLOR = 1, T2V_AUG_TRANSLATION = 2, T2V_AUG_CUTOUT = 4 };
+typedef struct t2v_aug_member {
+    const float* x;      /* fwd: the clips; bwd: dL/dy */
+    float* y;            /* fwd: the augmented clips; bwd: dL/dx */
+    const float* u;      /* parameter block [rows, T2V_AUG_K] */
+    int32_t N, C, T, S;
+    int32_t row_stride;  /* 2^level under --subsample_input (level sample j was sub-sampled from base sample j * 2^level), else 1 */
+    int32_t rows, policy, reserved;
+} t2v_aug_member;
+int t2v_diffaug_fwd(const t2v_aug_member* members, int n, void* stream);
+int t2v_diffaug_bwd(const t2v_aug_member* members, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

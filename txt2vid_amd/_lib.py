@@ -82,6 +82,12 @@ class WgradDest(C.Structure):
                 ('src', WgradSrc * WGRAD_MAX_SRC)]
 
 
+class AugMember(C.Structure):
+    """t2v_aug_member (include/t2v_hip.h)."""
+    _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('u', C.c_void_p), ('N', C.c_int32), ('C', C.c_int32), ('T', C.c_int32),
+                ('S', C.c_int32), ('row_stride', C.c_int32), ('rows', C.c_int32), ('policy', C.c_int32), ('reserved', C.c_int32)]
+
+
 MAX_GROUPS = 8
 _P = C.c_void_p
 _I = C.c_int
@@ -222,6 +228,8 @@ SIGNATURES = {
     't2v_tseed_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     't2v_ca_fwd': [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     't2v_ca_bwd': [_P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
+    't2v_diffaug_fwd': [_P, _I, _P],
+    't2v_diffaug_bwd': [_P, _I, _P],
     't2v_prof_begin': [_I],
     't2v_prof_end': [C.POINTER(C.c_double), _I],
     't2v_version': [],

@@ -1,0 +1,219 @@
+// diffaug.hip — differentiable augmentation of the discriminator's inputs (DiffAugment, Zhao et al. 2020; opt-in through
+// --D_aug, not in the reference), gfx950. One grouped launch per direction: every member tensor of a step (the real and the
+// generated pyramid, up to T2V_MAX_GROUPS) is transformed per clip with the colour / translation / cutout map defined in
+// include/t2v_hip.h and txt2vid_amd/functional_aug.py (`aug_params`). Launch-bound work (a pyramid level has 32 K elements at
+// the benchmarked shapes): plain vector loads and stores, the clip reduction and the apply step in the same launch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/t2v_hip.h"
+
+#define T2V_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+#define S_(stream) ((hipStream_t)(stream))
+
+static inline int launch_status() {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? T2V_OK : -(int)e - 1000;
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// block-wide sum for 256 threads in a fixed order; every thread gets the result
+__device__ __forceinline__ float block_sum(float v, float* red /*4 floats*/) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+#define AUG_MAX_PARTS 16          // workgroups one clip is split over, at most
+#define AUG_PART_ELEMS 8192       // elements of a clip per workgroup before it is split
+
+struct AugBatch {
+    t2v_aug_member m[T2V_MAX_GROUPS];
+    int begin[T2V_MAX_GROUPS + 1];      // first workgroup of member g; a member owns N * parts[g] workgroups
+    int parts[T2V_MAX_GROUPS];
+    int n;
+};
+
+struct AugP {
+    float b, s, c;            // brightness offset, saturation factor, contrast factor
+    int tx, ty;               // out(h, w) = in(h - ty, w - tx)
+    int x0, y0, size;         // zeroed box [x0, x0 + size) x [y0, y0 + size); size 0: none
+};
+// min(floor(u * n), n - 1) with the product exact (a 24-bit significand times a small integer fits a double)
+__device__ __forceinline__ int aug_index(float u, int n) {
+    int k = (int)floor((double)u * (double)n);
+    k = k < 0 ? 0 : k;
+    return k < n - 1 ? k : n - 1;
+}
+// the device mirror of functional_aug.aug_params
+__device__ __forceinline__ AugP aug_params(const float* __restrict__ u, int S, int policy) {
+    AugP p;
+    p.b = 0.f; p.s = 1.f; p.c = 1.f; p.tx = p.ty = 0; p.x0 = p.y0 = 0; p.size = 0;
+    if (policy & T2V_AUG_COLOR) { p.b = u[0] - 0.5f; p.s = 2.f * u[1]; p.c = u[2] + 0.5f; }
+    if (policy & T2V_AUG_TRANSLATION) {
+        const int r = (S + 4) / 8;
+        p.tx = aug_index(u[3], 2 * r + 1) - r;
+        p.ty = aug_index(u[4], 2 * r + 1) - r;
+    }
+    if (policy & T2V_AUG_CUTOUT) {
+        p.size = (S + 1) / 2;
+        const int n = S + 1 - (p.size & 1);
+        p.x0 = aug_index(u[5], n) - p.size / 2;
+        p.y0 = aug_index(u[6], n) - p.size / 2;
+    }
+    return p;
+}
+__device__ __forceinline__ bool aug_cut(const AugP& p, int h, int w) {
+    return (unsigned)(w - p.x0) < (unsigned)p.size && (unsigned)(h - p.y0) < (unsigned)p.size;
+}
+
+// Which member, clip and part of the clip this workgroup serves.
+#define AUG_LOCATE()                                                                       \
+    int g = 0;                                                                             \
+    while (g + 1 < tb.n && tb.begin[g + 1] <= (int)blockIdx.x) ++g;                        \
+    const t2v_aug_member& m = tb.m[g];                                                     \
+    const int parts = tb.parts[g];                                                         \
+    const int local = (int)blockIdx.x - tb.begin[g];                                       \
+    const int clip = local / parts, part = local - clip * parts;                           \
+    const int S = m.S, C = m.C, policy = m.policy;                                         \
+    const int V = m.T * S * S;                 /* voxels of one channel */                 \
+    const int n = C * V;                       /* elements of the clip  */                 \
+    const AugP p = aug_params(m.u + (long)clip * m.row_stride * T2V_AUG_K, S, policy);     \
+    const int per = (V + parts - 1) / parts;                                               \
+    const int v0 = part * per, v1 = min(V, v0 + per)
+
+__global__ __launch_bounds__(256) void diffaug_fwd_k(AugBatch tb) {
+    __shared__ float red[4];
+    AUG_LOCATE();
+    const float* __restrict__ x = m.x + (long)clip * n;
+    float* __restrict__ y = m.y + (long)clip * n;
+    float mu = 0.f;
+    if (policy & T2V_AUG_COLOR) {
+        // saturation keeps the channel mean: mu = mean(x) + b needs the clip sum of the input only. Every part of a clip sums the
+        // whole clip (L2-resident) in the same order.
+        float acc = 0.f;
+        const int nv = (((uintptr_t)x & 15) == 0) ? (n >> 2) : 0;
+        for (int q = threadIdx.x; q < nv; q += 256) {
+            const float4 a = reinterpret_cast<const float4*>(x)[q];
+            acc += (a.x + a.y) + (a.z + a.w);
+        }
+        for (int i = nv * 4 + threadIdx.x; i < n; i += 256) acc += x[i];
+        mu = block_sum(acc, red) / (float)n + p.b;
+    }
+    const float invC = 1.f / (float)C;
+    for (int v = v0 + threadIdx.x; v < v1; v += 256) {
+        const int w = v % S, h = (v / S) % S;
+        const int hs = h - p.ty, ws = w - p.tx;
+        if (aug_cut(p, h, w) || (unsigned)hs >= (unsigned)S || (unsigned)ws >= (unsigned)S) {
+            for (int c = 0; c < C; ++c) y[(long)c * V + v] = 0.f;
+            continue;
+        }
+        const int src = v - (h * S + w) + hs * S + ws;
+        if (!(policy & T2V_AUG_COLOR)) {
+            for (int c = 0; c < C; ++c) y[(long)c * V + v] = x[(long)c * V + src];
+            continue;
+        }
+        float mc = x[src];
+        if (C > 1) {
+            for (int c = 1; c < C; ++c) mc += x[(long)c * V + src];
+            mc *= invC;
+        }
+        for (int c = 0; c < C; ++c) {
+            const float xv = x[(long)c * V + src];
+            const float t = (xv - mc) * p.s + (mc + p.b);
+            y[(long)c * V + v] = (t - mu) * p.c + mu;
+        }
+    }
+}
+
+// dL/dx from dL/dy (m.x -> m.y). gcol = the gradient masked by the cutout and shifted back; then the colour map's adjoint.
+__global__ __launch_bounds__(256) void diffaug_bwd_k(AugBatch tb) {
+    __shared__ float red[4];
+    AUG_LOCATE();
+    const float* __restrict__ gy = m.x + (long)clip * n;
+    float* __restrict__ gx = m.y + (long)clip * n;
+    float gm = 0.f;
+    if (policy & T2V_AUG_COLOR) {
+        // clip sum of gcol = sum of dL/dy over the output voxels that are not cut and whose source lies inside the frame
+        float acc = 0.f;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int v = i % V, w = v % S, h = (v / S) % S;
+            const bool keep = !aug_cut(p, h, w) && (unsigned)(h - p.ty) < (unsigned)S && (unsigned)(w - p.tx) < (unsigned)S;
+            acc += keep ? gy[i] : 0.f;
+        }
+        gm = block_sum(acc, red) / (float)n;
+    }
+    const float invC = 1.f / (float)C;
+    const float rest = (1.f - p.c) * gm;
+    for (int v = v0 + threadIdx.x; v < v1; v += 256) {
+        const int w = v % S, h = (v / S) % S;
+        const int ho = h + p.ty, wo = w + p.tx;
+        const bool valid = (unsigned)ho < (unsigned)S && (unsigned)wo < (unsigned)S && !aug_cut(p, ho, wo);
+        const int dst = v - (h * S + w) + ho * S + wo;
+        if (!(policy & T2V_AUG_COLOR)) {
+            for (int c = 0; c < C; ++c) gx[(long)c * V + v] = valid ? gy[(long)c * V + dst] : 0.f;
+            continue;
+        }
+        if (C == 1) {
+            gx[v] = p.c * (valid ? gy[dst] : 0.f) + rest;
+            continue;
+        }
+        float gc = 0.f;
+        if (valid) for (int c = 0; c < C; ++c) gc += gy[(long)c * V + dst];
+        const float pm = p.c * (gc * invC) + rest;                  // mean over channels of the contrast adjoint
+        for (int c = 0; c < C; ++c) {
+            const float g2 = p.c * (valid ? gy[(long)c * V + dst] : 0.f) + rest;
+            gx[(long)c * V + v] = p.s * g2 + (1.f - p.s) * pm;
+        }
+    }
+}
+
+static int aug_batch(AugBatch& tb, const t2v_aug_member* ms, int n, long* blocks_out) {
+    if (!ms || n < 1 || n > T2V_MAX_GROUPS) return T2V_EINVAL;
+    long blocks = 0;
+    for (int g = 0; g < T2V_MAX_GROUPS; ++g) {
+        tb.begin[g] = (int)blocks;
+        tb.parts[g] = 1;
+        if (g >= n) { tb.m[g] = t2v_aug_member{}; continue; }
+        const t2v_aug_member& q = ms[g];
+        if (!q.x || !q.y || !q.u || q.x == q.y || q.N < 1 || q.C < 1 || q.T < 1 || q.S < 1) return T2V_EINVAL;
+        if (q.policy < 1 || (q.policy & ~(T2V_AUG_COLOR | T2V_AUG_TRANSLATION | T2V_AUG_CUTOUT))) return T2V_EINVAL;
+        if (q.row_stride < 1 || q.rows < 1 || (long)(q.N - 1) * q.row_stride >= (long)q.rows) return T2V_EINVAL;
+        const long V = (long)q.T * q.S * q.S, elems = V * q.C;
+        if (q.S > 32768 || elems > 0x40000000L) return T2V_EINVAL;
+        long parts = (elems + AUG_PART_ELEMS - 1) / AUG_PART_ELEMS;
+        parts = parts > AUG_MAX_PARTS ? AUG_MAX_PARTS : parts;
+        parts = parts > V ? V : parts;
+        tb.m[g] = q;
+        tb.parts[g] = (int)parts;
+        blocks += (long)q.N * parts;
+        if (blocks > 0x7fffffffL) return T2V_EINVAL;
+    }
+    tb.begin[T2V_MAX_GROUPS] = (int)blocks;
+    tb.n = n;
+    *blocks_out = blocks;
+    return T2V_OK;
+}
+
+extern "C" int t2v_diffaug_fwd(const t2v_aug_member* members, int n, void* st) {
+    AugBatch tb;
+    long blocks = 0;
+    const int rc = aug_batch(tb, members, n, &blocks);
+    if (rc != T2V_OK) return rc;
+    T2V_LAUNCH(diffaug_fwd_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
+    return launch_status();
+}
+
+extern "C" int t2v_diffaug_bwd(const t2v_aug_member* members, int n, void* st) {
+    AugBatch tb;
+    long blocks = 0;
+    const int rc = aug_batch(tb, members, n, &blocks);
+    if (rc != T2V_OK) return rc;
+    T2V_LAUNCH(diffaug_bwd_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
+    return launch_status();
+}

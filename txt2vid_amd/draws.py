@@ -14,6 +14,8 @@ import os as _os
 
 _UPLOAD_BY_MEMCPY = _os.environ.get('T2V_DRAWS_MEMCPY') is not None
 
+AUG_K = 8           # uniforms per sample of one augmentation block (functional_aug.K)
+
 
 class HostDraws(object):
     def multiscale_t0(self, n):
@@ -38,6 +40,10 @@ class HostDraws(object):
         """eps ~ N(0, 1) [b, d] of the generator's conditioning augmentation (one draw per generator forward, like z)."""
         return torch.randn(b, d).to(device, non_blocking=True)
 
+    def aug(self, b, device):
+        """One block u [b, AUG_K] of uniforms for an augmentation of D's inputs (functional_aug), drawn when it is consumed."""
+        return torch.rand(b, AUG_K).to(device, non_blocking=True)
+
     def perm(self, n, device):
         """A non-identity permutation of range(n) from numpy's global RNG (util/misc.gen_perm), as a device int32 tensor."""
         import numpy as _np
@@ -47,27 +53,35 @@ class HostDraws(object):
 
 class StaticDraws(object):
     def __init__(self, device, batch, latent, n_levels, n_gen_phases=3, gp=True, subsample_input=True, n_perms=0,
-                 n_d_steps=1, n_g_steps=1, ca_dim=0):
+                 n_d_steps=1, n_g_steps=1, ca_dim=0, n_aug=0):
         self.n_perms = n_perms                      # caption permutations per iteration (conditional path: D steps, real_pred)
         self.n_d_steps, self.n_g_steps = n_d_steps, n_g_steps     # one set of GP alphas per D step, of G phases per G forward
         self._p = 0
         self.device, self.batch, self.latent = device, batch, latent
         self.ca_dim = ca_dim                        # conditioning augmentation: one eps [batch, ca_dim] per G forward (0: none)
         self.n_levels, self.n_gen, self.gp, self.sub = n_levels, n_gen_phases, gp, subsample_input
+        # augmentation of D's inputs (--D_aug): blocks [batch, AUG_K] per iteration, in the eager order of consumption — a real and
+        # a generated block per D step and at G part 0, a generated block per later G step (0: none, today's layout)
+        if n_aug not in (0, 2 * n_d_steps + n_g_steps + 1):
+            raise ValueError('an iteration of %d D and %d G steps consumes %d augmentation blocks, not %d'
+                             % (n_d_steps, n_g_steps, 2 * n_d_steps + n_g_steps + 1, n_aug))
+        self.n_aug = n_aug
         self.bs = [batch]
         for _ in range(n_levels - 1):
             self.bs.append((self.bs[-1] + 1) // 2)
         # one pinned staging buffer and one device buffer of 32-bit words for every draw of an iteration (int32 phases |
-        # float32 z | float32 alphas | int32 caption permutations | float32 CA eps of every G forward, absent without CA): ONE H2D
+        # float32 z | float32 alphas | int32 caption permutations | float32 CA eps of every G forward, absent without CA | float32
+        # augmentation blocks, absent without --D_aug): ONE H2D
         # copy node per replayed iteration instead of four (a copy node costs ~20 us of idle time in the replayed graph)
         n_int, n_z, n_a, n_p = n_levels + n_gen_phases * n_g_steps, batch * latent, sum(self.bs) * n_d_steps, max(1, n_perms) * batch
         n_e = batch * ca_dim * n_g_steps
+        n_u = batch * AUG_K * n_aug
         # The staging side is a RING of pinned buffers: the upload is asynchronous and the training loop runs the host ahead of
         # the GPU (losses are read one iteration late), so a single staging buffer would be rewritten with iteration i + 1's draws
         # before the copy of iteration i has executed. A slot is reused only after the event behind its last copy has completed.
         self.RING = 4
         on_gpu = torch.device(device).type != 'cpu'        # (a CPU "device": the host-side draw order alone, no pinned memory)
-        self.h_ring = [torch.zeros(n_int + n_z + n_a + n_p + n_e, dtype=torch.int32) for _ in range(self.RING)]
+        self.h_ring = [torch.zeros(n_int + n_z + n_a + n_p + n_e + n_u, dtype=torch.int32) for _ in range(self.RING)]
         if on_gpu:
             self.h_ring = [h.pin_memory() for h in self.h_ring]
         self.h_events = [None] * self.RING
@@ -82,24 +96,28 @@ class StaticDraws(object):
             a_ = buf[o:o + n_a].view(torch.float32); o += n_a
             p_ = buf[o:o + n_p].view(max(1, n_perms), batch); o += n_p
             e_ = buf[o:o + n_e].view(torch.float32).view(n_g_steps, batch, ca_dim) if n_e else None
-            return i_, z_, a_, p_, e_
+            o += n_e
+            u_ = buf[o:o + n_u].view(torch.float32).view(n_aug, batch, AUG_K) if n_u else None
+            return i_, z_, a_, p_, e_, u_
         self._carve = carve
-        self.h_int, self.h_z, self.h_a, self.h_perm, self.h_eps = carve(self.h_all)
-        self.d_int, self.d_z, self.d_a, self.d_perm, self.d_eps = carve(self.d_all)
-        self._i = self._a = self._e = 0
+        self.h_int, self.h_z, self.h_a, self.h_perm, self.h_eps, self.h_u = carve(self.h_all)
+        self.d_int, self.d_z, self.d_a, self.d_perm, self.d_eps, self.d_u = carve(self.d_all)
+        self._i = self._a = self._e = self._u = 0
 
     def begin_step(self):
         """All host draws of one iteration, reference order (trainer.py:221-263): n_levels Subsample phases, z, the generator's
         phases of its first forward, the GP alphas per level of every D step, the generator's phases of every later G
         forward; numpy: the caption permutations in the order they are consumed. Then one small H2D copy on the current
         stream. With conditioning augmentation every G forward draws its eps first, in front of its phases: z, eps 0, phases 0,
-        alphas, then eps j, phases j for each later forward j."""
+        alphas, then eps j, phases j for each later forward j. With augmentation of D's inputs every D step draws a real and a
+        generated block in front of its alphas, G part 0 draws a real and a generated block behind the last D step, and every later
+        G forward j draws a generated block behind its phases."""
         slot = self._slot
         self._slot = (slot + 1) % self.RING
         if self.h_events[slot] is not None:
             self.h_events[slot].synchronize()            # (the copy that last read this slot is done; normally long ago)
         self.h_all = self.h_ring[slot]
-        self.h_int, self.h_z, self.h_a, self.h_perm, self.h_eps = self._carve(self.h_all)
+        self.h_int, self.h_z, self.h_a, self.h_perm, self.h_eps, self.h_u = self._carve(self.h_all)
         t0, st = 0, 1
         for l in range(self.n_levels):
             self.h_int[l] = t0
@@ -111,17 +129,28 @@ class StaticDraws(object):
             self.h_eps[0].copy_(torch.randn(self.batch, self.ca_dim))
         for k in range(self.n_gen):
             self.h_int[self.n_levels + k] = int(torch.randint(2, (1,)))
-        if self.gp:
-            off = 0
-            for _ in range(self.n_d_steps):
+        off = blk = 0
+        for _ in range(self.n_d_steps):
+            if self.n_aug:
+                self.h_u[blk].copy_(torch.rand(self.batch, AUG_K))
+                self.h_u[blk + 1].copy_(torch.rand(self.batch, AUG_K))
+                blk += 2
+            if self.gp:
                 for b in self.bs:
                     self.h_a[off:off + b] = torch.rand(b, 1, 1, 1, 1).reshape(b)
                     off += b
+        if self.n_aug:
+            self.h_u[blk].copy_(torch.rand(self.batch, AUG_K))
+            self.h_u[blk + 1].copy_(torch.rand(self.batch, AUG_K))
+            blk += 2
         for j in range(1, self.n_g_steps):
             if self.ca_dim:
                 self.h_eps[j].copy_(torch.randn(self.batch, self.ca_dim))
             for k in range(self.n_gen * j, self.n_gen * (j + 1)):
                 self.h_int[self.n_levels + k] = int(torch.randint(2, (1,)))
+            if self.n_aug:
+                self.h_u[blk].copy_(torch.rand(self.batch, AUG_K))
+                blk += 1
         if self.n_perms:
             from .util.misc import gen_perm
             for k in range(self.n_perms):
@@ -138,7 +167,7 @@ class StaticDraws(object):
             ev = torch.cuda.Event()
             ev.record()
             self.h_events[slot] = ev
-        self._i = self._a = self._p = self._e = 0
+        self._i = self._a = self._p = self._e = self._u = 0
 
     def multiscale_t0(self, n):
         assert n == self.n_levels
@@ -169,5 +198,11 @@ class StaticDraws(object):
         self._e += 1
         return self.d_eps[k]
 
+    def aug(self, b, device):
+        assert b == self.batch and self._u < self.n_aug
+        k = self._u
+        self._u += 1
+        return self.d_u[k]
+
     def rewind(self):
-        self._i = self._a = self._p = self._e = 0
+        self._i = self._a = self._p = self._e = self._u = 0

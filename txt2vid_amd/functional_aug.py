@@ -1,0 +1,133 @@
+"""Differentiable augmentation of the discriminator's inputs (DiffAugment, Zhao et al. 2020; opt-in through `--D_aug`, not in the
+reference): the shared definition of the transformation and the autograd surface of its two grouped kernels
+(csrc/diffaug.hip `t2v_diffaug_fwd` / `t2v_diffaug_bwd`). DESIGN §17.
+
+THE DEFINITION (kernels, `aug_params` and the tests' restatement all follow it). The policy is a subset of
+color, translation, cutout, applied in that order, one transformation per clip [C, T, S, S], constant over its frames. A call
+consumes one block u [B, K] of uniforms in [0, 1), K = 8, one row per base sample:
+
+    column 0  brightness   x + b,              b = u0 - 0.5
+    column 1  saturation   (x - m) s + m,      s = 2 u1,     m = the voxel's mean over channels   (identity for C = 1)
+    column 2  contrast     (x - mu) c + mu,    c = u2 + 0.5, mu = the mean of the whole clip after brightness and saturation
+                                                              = mean(input clip) + b  (saturation keeps the channel mean)
+    column 3  tx = min(floor(u3 (2r + 1)), 2r) - r,  r = floor(S / 8 + 0.5)
+    column 4  ty, the same from u4;            out(h, w) = in(h - ty, w - tx), 0 outside the frame
+    column 5  cx = min(floor(u5 n), n - 1),    size = floor(S / 2 + 0.5), n = S + 1 - size % 2
+    column 6  cy, the same from u6;            out = 0 for columns in [cx - size // 2, cx - size // 2 + size) and rows in the same
+                                               range around cy
+    column 7  unused (it pads a row to 32 bytes)
+
+The products u3 (2r + 1), u5 n, ... are taken EXACTLY (an fp32 value times a small integer; float64 holds it), so the integer
+parameters are the same on every side. Pyramid level l re-derives the integers from the same row for its own S; under
+--subsample_input sample j of level l reads the row of base sample j * 2^l, the sample it was sub-sampled from, so a clip gets
+the same transformation at every scale.
+
+The map is affine per clip. Adjoint: mask and shift the incoming gradient back, then contrast c g + (1 - c) mean_clip(g), then
+saturation s g + (1 - s) mean_channels(g); brightness is the identity. The backward is ONCE differentiable: the gradient
+penalty's interpolates are formed from the already augmented clips and stay leaves, so no second-order adjoint is needed.
+fp32 whatever the convolution precision.
+"""
+import torch
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+from ._lib import AugMember, MAX_GROUPS
+from ._ops import _stream, _c, lib, check
+
+K = 8                                                     # uniforms per base sample (T2V_AUG_K)
+COLOR, TRANSLATION, CUTOUT = 1, 2, 4                      # policy bits (T2V_AUG_*)
+NAMES = ('color', 'translation', 'cutout')
+
+
+def parse_policy(text):
+    """'color,cutout' -> policy bits ('' or None -> 0). ValueError on an unknown or empty name."""
+    if not text:
+        return 0
+    bits = 0
+    for name in str(text).split(','):
+        name = name.strip()
+        if name not in NAMES:
+            raise ValueError('unknown augmentation %r (choose from %s)' % (name, ', '.join(NAMES)))
+        bits |= 1 << NAMES.index(name)
+    return bits
+
+
+def _index(u, n):
+    """min(floor(u n), n - 1) as int64, the product taken exactly in float64."""
+    return torch.clamp(torch.floor(u.double() * n).long(), 0, n - 1)
+
+
+def aug_params(u, S):
+    """The parameters of one block u [B, K] (fp32) for frames of side S, per base sample: a dict of
+    b, s, c (float64, exact functions of the fp32 draws), tx, ty (int64 in [-r, r]), x0, y0 (int64, first column / row of the cut
+    box, may be negative) and size, r (ints)."""
+    if u.dim() != 2 or u.shape[1] != K:
+        raise ValueError('an augmentation block is [B, %d], got %s' % (K, tuple(u.shape)))
+    S = int(S)
+    r = (S + 4) // 8                                   # floor(S / 8 + 0.5)
+    size = (S + 1) // 2                                # floor(S / 2 + 0.5)
+    n = S + 1 - size % 2
+    ud = u.double()
+    return dict(b=ud[:, 0] - 0.5, s=2.0 * ud[:, 1], c=ud[:, 2] + 0.5,
+                tx=_index(u[:, 3], 2 * r + 1) - r, ty=_index(u[:, 4], 2 * r + 1) - r,
+                x0=_index(u[:, 5], n) - size // 2, y0=_index(u[:, 6], n) - size // 2, size=size, r=r)
+
+
+def _members(srcs, dsts, us, strides, policy):
+    arr = (AugMember * len(srcs))()
+    for a, x, y, u, st in zip(arr, srcs, dsts, us, strides):
+        N, Cc, T, H, W = x.shape
+        a.x, a.y, a.u = x.data_ptr(), y.data_ptr(), u.data_ptr()
+        a.N, a.C, a.T, a.S = N, Cc, T, H
+        a.row_stride, a.rows, a.policy = int(st), int(u.shape[0]), policy
+    return arr
+
+
+class DiffAug(Function):
+    """ys = T(xs): ONE forward launch for all members; ONE backward launch over the members that require a gradient (none: no
+    launch). The parameter blocks carry no gradient (host draws)."""
+
+    @staticmethod
+    def forward(ctx, policy, us, strides, *xs):
+        if not 1 <= len(xs) <= MAX_GROUPS:
+            raise ValueError('1 to %d tensors per augmentation launch, got %d' % (MAX_GROUPS, len(xs)))
+        if len(us) != len(xs) or len(strides) != len(xs):
+            raise ValueError('one parameter block and one row stride per tensor')
+        xs = [_c(x) for x in xs]
+        us = [_c(u) for u in us]
+        for x, u in zip(xs, us):
+            if x.dim() != 5 or x.shape[3] != x.shape[4]:
+                raise ValueError('augmentation takes clips [N, C, T, S, S] with square frames, got %s' % (tuple(x.shape),))
+            if u.dim() != 2 or u.shape[1] != K:
+                raise ValueError('an augmentation block is [B, %d], got %s' % (K, tuple(u.shape)))
+        ys = [torch.empty_like(x) for x in xs]
+        check(lib().t2v_diffaug_fwd(_members(xs, ys, us, strides, policy), len(xs), _stream()), 't2v_diffaug_fwd')
+        ctx.set_materialize_grads(False)
+        ctx.cfg = (policy, tuple(strides))
+        ctx.us = us                                    # (plain tensors that never require grad: no saved-tensor hooks needed)
+        ctx.mark_non_differentiable(*[y for y, need in zip(ys, ctx.needs_input_grad[3:]) if not need])
+        return tuple(ys)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gys):
+        policy, strides = ctx.cfg
+        live = [i for i, g in enumerate(gys) if g is not None and ctx.needs_input_grad[3 + i]]
+        gxs = [None] * len(gys)
+        if live:
+            gs = [_c(gys[i]) for i in live]
+            outs = [torch.empty_like(g) for g in gs]
+            check(lib().t2v_diffaug_bwd(_members(gs, outs, [ctx.us[i] for i in live], [strides[i] for i in live], policy),
+                                        len(live), _stream()), 't2v_diffaug_bwd')
+            for i, o in zip(live, outs):
+                gxs[i] = o
+        return (None, None, None) + tuple(gxs)
+
+
+def diffaug(xs, us, strides, policy):
+    """Augment the clips `xs` (a list of [N, C, T, S, S] device tensors) in one launch; member i reads row j * strides[i] of its
+    block us[i] [B, K] for its clip j. `policy`: bits or a comma-separated string. Returns the list of augmented clips."""
+    bits = parse_policy(policy) if isinstance(policy, str) else int(policy)
+    if not bits:
+        return list(xs)
+    return list(DiffAug.apply(bits, tuple(us), tuple(strides), *xs))

@@ -6,7 +6,9 @@ Random draws follow the reference order on the HOST generators (SURVEY §7 "RNG 
 phase (trainer.py:157-158), z (trainer.py:221, drawn on the CPU and copied), 3x Subsample in G,
 gen_perm (numpy), 4x GP alpha (losses.py:140-145), gen_perm for real_pred (trainer.py:247). Under the
 --discrim_steps N / --gen_steps M schedule (trainer.py:228-263): gen_perm + 4x alpha once per D step, then
-gen_perm for real_pred, then 3x Subsample per later G forward (DESIGN "D:G step schedule").
+gen_perm for real_pred, then 3x Subsample per later G forward (DESIGN "D:G step schedule"). With --D_aug every D step
+draws a real and a generated augmentation block in front of its alphas, G part 0 a real and a generated block, every later G
+step a generated block behind its forward's draws.
 """
 import argparse
 import os
@@ -28,9 +30,18 @@ def _ema_decay(text):
     return v
 
 
+def _aug_policy(text):
+    from ..functional_aug import parse_policy
+    try:
+        parse_policy(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError('--D_aug: %s' % e)
+    return text
+
+
 def add_params_to_parser(parser):
-    """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema and
-    --G_ema_start are new."""
+    """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema,
+    --G_ema_start and --D_aug are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
     parser.add_argument('--log_period', type=int, default=20)
@@ -54,6 +65,9 @@ def add_params_to_parser(parser):
                         help='(new) decay of a moving average of the generator weights, used for samples and saved as gen_ema; 0 = off')
     parser.add_argument('--G_ema_start', type=int, default=0,
                         help='(new) the average copies the weights for the first N generator updates')
+    parser.add_argument('--D_aug', type=_aug_policy, default='',
+                        help='(new) differentiable augmentation of every clip the discriminator sees: a comma-separated subset of '
+                             'color,translation,cutout (applied in that order); empty = off')
     return parser
 
 
@@ -119,6 +133,12 @@ class TrainStep(object):
         self.ca = bool(getattr(gen, 'ca_dim', 0))
         self.kl_coeff = float(getattr(gen, 'ca_kl_coeff', 0.0)) if self.ca else 0.0
         self.lKL = self._kl = None
+        # differentiable augmentation of D's inputs (--D_aug, not in the reference; functional_aug): every list of clips handed to
+        # discrim_step / gen_step / gen_step_fused / the real_pred pass goes through ONE grouped launch first (real + generated),
+        # with fresh parameter blocks per D step and per G step. Parameter objects without the attribute mean "off".
+        from ..functional_aug import parse_policy
+        self.aug = parse_policy(getattr(params, 'D_aug', ''))
+        self._xs_g = None                 # the augmented real pyramid of G part 0 (reused by later fused G steps)
         self._fused = False
         self._one = None                  # dL/dL = 1 for both backward passes: one persistent 0-d tensor (no fill launch per pass)
         # the store_false quirk of --no_mean_*_loss (trainer.py:236-237,260-261): the loss of every step is divided by the step
@@ -169,11 +189,31 @@ class TrainStep(object):
             return fake
         return self.gan(self._z, cond=cond)
 
+    def _augment(self, real, fake):
+        """(real, fake) through the augmentation, both lists (either may be None) in one launch: a block of draws for the real
+        clips first, then one for the generated clips. Under --subsample_input level l's sample j reads base row j * 2^l."""
+        if not self.aug:
+            return real, fake
+        from ..functional_aug import diffaug
+        xs, us, strides = [], [], []
+        for clips in (real, fake):
+            if clips is None:
+                continue
+            u = TF.draws.aug(self._batch, self.device)
+            for l, t in enumerate(clips):
+                xs.append(t)
+                us.append(u)
+                strides.append(2 ** l if self.params.subsample_input else 1)
+        out = diffaug(xs, us, strides, self.aug)
+        n = len(real) if real is not None else 0
+        return (out[:n] if real is not None else None), (out[n:] if fake is not None else None)
+
     def _d_step(self, arm=True):
         p = self.params
         if arm:
             self._arm_sink()
-        loss = self.gan.discrim_step(real=self.xs, fake=[f.detach() for f in self.fake], cond=self.conds,
+        real, fake = self._augment(self.xs, [f.detach() for f in self.fake])
+        loss = self.gan.discrim_step(real=real, fake=fake, cond=self.conds,
                                      loss=self.losses.discrim_loss, gp_lambda=p.gp_lambda)
         loss.backward(gradient=self._root(loss, self.d_scale), retain_graph=self.end2end)
         TF.grad_sink_flush()              # the weight-gradient partial sums of the whole pass, summed in one launch
@@ -182,7 +222,8 @@ class TrainStep(object):
     def part_d(self, x, cond):
         """D part 0: pyramid, z, G forward and the first D step."""
         p = self.params
-        self.lD = self.lG = self._real_pred = self.lKL = None
+        self.lD = self.lG = self._real_pred = self.lKL = self._xs_g = None
+        self._batch = x.size(0)
         self._arm_sink()
         self.xs, self.conds = multiscale_data(x, cond, p.frame_sizes, p.subsample_input)
         self._z = TF.draws.z(x.size(0), self.gan.gen.latent_size, self.device)       # CPU generator, then copy (parity)
@@ -201,18 +242,21 @@ class TrainStep(object):
         # D after its update, on the real batch (trainer.py:247). Its graph is only needed when the text
         # encoder trains end-to-end; otherwise nothing upstream of these predictions receives a gradient
         # that is ever used, so none is recorded (identical results, SURVEY §7 "wasted work").
-        self._fused = not self.end2end and self.gan.can_fuse_gen_step(self.fake, self.xs)
+        xs, fake = self._augment(self.xs, self.fake)
+        self._fused = not self.end2end and self.gan.can_fuse_gen_step(fake, xs)
         if self._fused:
-            loss = self.gan.gen_step_fused(fake=self.fake, real=self.xs, cond=self.conds, loss=self.losses.gen_loss, **self._kl_args())
+            if self.n_g > 1:
+                self._xs_g = xs
+            loss = self.gan.gen_step_fused(fake=fake, real=xs, cond=self.conds, loss=self.losses.gen_loss, **self._kl_args())
         else:
             if self.end2end:
-                _, _, real_pred = self.gan.all_discrim_forward(real=self.xs, cond=self.conds, fake=None, loss=None)
+                _, _, real_pred = self.gan.all_discrim_forward(real=xs, cond=self.conds, fake=None, loss=None)
             else:
                 with torch.no_grad():
-                    _, _, real_pred = self.gan.all_discrim_forward(real=self.xs, cond=self.conds, fake=None, loss=None)
+                    _, _, real_pred = self.gan.all_discrim_forward(real=xs, cond=self.conds, fake=None, loss=None)
             if self.n_g > 1:
                 self._real_pred = real_pred
-            loss = self.gan.gen_step(fake=self.fake, real_pred=real_pred, cond=self.conds, loss=self.losses.gen_loss,
+            loss = self.gan.gen_step(fake=fake, real_pred=real_pred, cond=self.conds, loss=self.losses.gen_loss,
                                      **self._kl_args())
         self._g_backward(loss, last=self.n_g == 1)
 
@@ -223,11 +267,12 @@ class TrainStep(object):
         self._g_update()
         self._arm_sink()
         self.fake = self._forward_g()
+        _, fake = self._augment(None, self.fake)          # (the real clips keep G part 0's transformation)
         if self._fused:
-            loss = self.gan.gen_step_fused(fake=self.fake, real=self.xs, cond=self.conds, loss=self.losses.gen_loss,
+            loss = self.gan.gen_step_fused(fake=fake, real=self._xs_g, cond=self.conds, loss=self.losses.gen_loss,
                                            draw_perm=False, **self._kl_args())
         else:
-            loss = self.gan.gen_step(fake=self.fake, real_pred=self._real_pred, cond=self.conds, loss=self.losses.gen_loss,
+            loss = self.gan.gen_step(fake=fake, real_pred=self._real_pred, cond=self.conds, loss=self.losses.gen_loss,
                                      **self._kl_args())
         self._g_backward(loss, last)
 
@@ -243,7 +288,7 @@ class TrainStep(object):
             self.lKL = self._total(self.lKL, self._kl, self.g_scale)
             self._kl = None
         if last:
-            self._real_pred = None
+            self._real_pred = self._xs_g = None
 
     def _g_update(self):
         """G's optimiser step and, when the generator's weights are averaged (--G_ema), the average's update right behind it
@@ -310,7 +355,8 @@ class GraphedTrainStep(object):
         self.draws = TF.StaticDraws(device, batch_shape[0], gan.gen.latent_size, n_levels, n_gen_phases=n_levels - 1,
                                     gp=params.gp_lambda > 0, subsample_input=params.subsample_input,
                                     n_perms=(N + 1) * len(gan.discrims) if cond_dim else 0, n_d_steps=N, n_g_steps=M,
-                                    ca_dim=getattr(gan.gen, 'ca_dim', 0) if cond_dim else 0)
+                                    ca_dim=getattr(gan.gen, 'ca_dim', 0) if cond_dim else 0,
+                                    n_aug=2 * N + M + 1 if self.ts.aug else 0)
         self.x = torch.empty(batch_shape, device=device, dtype=torch.float32)
         # conditional path: the sentence code is computed outside the graphs (its sequence length varies) into a fixed buffer
         self.cond = torch.empty((batch_shape[0], cond_dim), device=device, dtype=torch.float32) if cond_dim else None
@@ -330,7 +376,7 @@ class GraphedTrainStep(object):
             opt.make_capturable(self.device)
         # drop every reference into the previous iteration's autograd graph before capturing
         self.ts.lD = self.ts.lG = self.ts.fake = self.ts.xs = self.ts.conds = self.ts._real_pred = None
-        self.ts.lKL = self.ts._kl = None
+        self.ts.lKL = self.ts._kl = self.ts._xs_g = None
         torch.cuda.synchronize()
         self.draws.rewind()
         gs = self.grad_sync
