@@ -2,8 +2,9 @@
 (tests/test_conv_plan.py), plus host-side access to the launch-plan queries of the C ABI (`t2v_conv_fwd_plan`,
 `t2v_conv_wgrad_plan`: pure host arithmetic, no GPU needed).
 
-The kernel instantiation a convolution runs on is size-dependent (conv.hip `build_table` / `conv_variant` /
-`build_wtable`), so "the op is tested" does not imply "the instantiation the benchmark runs is tested". The lists here
+The kernel instantiation a convolution runs on is size-dependent (conv.hip `decide_fwd` / `decide_bf16` / `decide_wgrad` /
+`decide_pool_*`: one decision per launch, which the plan query serialises and the launcher runs), so "the op is tested" does
+not imply "the instantiation the benchmark runs is tested". The lists here
 make that explicit: SINGLE_CASES are small single-tensor shapes, GROUPED_CASES include the discriminator's grouped
 launches at the BENCHMARK size (BASELINE configs[1]: per-GPU batch 32, 16x64x64x1 clips)."""
 import ctypes as C

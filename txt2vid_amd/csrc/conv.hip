@@ -2622,38 +2622,85 @@ static bool thin_ok(const t2v_conv_group* groups, int ngroups, int Cin, int Cout
 // ------------------------------------------------------------------------------------------------
 // Launch-heuristic tunables, in ONE place. The defaults are the measured optima on MI355X. The environment
 // overrides exist for developer sweeps (tools/conv_suite.py) and for tests that force an instantiation onto a small input;
-// tests/test_conv_plan.py::test_environment_tunables_move_the_plan checks every one of them through the plan queries.
-// Read once, at the first launch or plan query of the process.
+// tests/test_conv_plan.py::test_environment_tunables_move_the_plan and tests/test_conv_plan_sweep.py check them through the
+// plan queries. Read once, at the first launch or plan query of the process.
 // ------------------------------------------------------------------------------------------------
 struct Tunables {
     long tile128_min;      // T2V_TILE128_MIN   (768)  128-voxel tiles from this many tiles on, else 64
     long tile256_min;      // T2V_TILE256_MIN   (512)  256-voxel tiles from this many tiles on
     long nosplit_chunks;   // T2V_NOSPLIT_CHUNKS  (8)  no split-K for reductions of at most this many K chunks
     long force_splits;     // T2V_FORCE_S         (0)  > 0: this split-K count for every forward / data-gradient launch
+    long split_target;     // T2V_SPLIT_TARGET  (768)  workgroups a split-K forward / data-gradient launch aims at
     bool strip;            // T2V_NO_STRIP unset       strip (three-dx-taps-per-row) kernels enabled
+    long strip3_db;        // T2V_STRIP3_DB      (16)  channels per round (16 / 32) of the double-buffered 64-voxel strip3 tile; else single-stage
+    bool strip3_db256;     // T2V_STRIP3_DB256    (1)  the double-buffered form of the 256-voxel strip3 tile
     bool occ_pad;          // T2V_NO_OCC_PAD unset     resident-workgroup choice of the 256-voxel tile (occupancy_pad)
     long wgrad_target;     // T2V_WGRAD_TARGET    (0)  weight-gradient workgroups to aim at; 0: 1024 = one round of resident workgroups
     long wgrad_scap;       // T2V_WGRAD_SCAP    (256)  upper bound of the weight-gradient k-split count
     bool wgrad_quantise;   // T2V_WGRAD_NOQ unset      drop a nearly empty last round of weight-gradient workgroups
     long wgrad_min_cps;    // T2V_WGRAD_MINCPS    (4)  fewest 32-voxel chunks a weight-gradient k-split may own
     bool wgrad_thin;       // T2V_NO_WGRAD_THIN unset  the streaming kernel for narrow inputs (<= 31 (tap, ci) columns)
+    // the double-buffered forms of the pooled GEMMs (16-channel rounds, one barrier per round; see conv_igemm_strip3_kernel): the forward
+    // takes it by default (-8 %), the data gradient does not (+3 % on its 2-8 round loops). Plan queries report K chunk 16, KS 2 for them.
+    bool pool_fwd_db;      // T2V_POOL_FWD_DB     (1)
+    bool pool_dgrad_db;    // T2V_POOL_DGRAD_DB   (0)
+    long pool_dgrad_split_below;   // T2V_POOL_DGRAD_SPLIT_BELOW (576)  the pooled data gradient splits K below this many tiles
+    long pool_wgrad_min_cps;       // T2V_POOL_WGRAD_MINCPS        (4)  wgrad_min_cps of the pooled weight gradient
 };
 static long env_long(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
 static const Tunables& tun() {
     static const Tunables t = {env_long("T2V_TILE128_MIN", 768), env_long("T2V_TILE256_MIN", 512), env_long("T2V_NOSPLIT_CHUNKS", 8),
-                               env_long("T2V_FORCE_S", 0), getenv("T2V_NO_STRIP") == nullptr, getenv("T2V_NO_OCC_PAD") == nullptr,
+                               env_long("T2V_FORCE_S", 0), env_long("T2V_SPLIT_TARGET", 768), getenv("T2V_NO_STRIP") == nullptr,
+                               env_long("T2V_STRIP3_DB", 16), env_long("T2V_STRIP3_DB256", 1) != 0, getenv("T2V_NO_OCC_PAD") == nullptr,
                                env_long("T2V_WGRAD_TARGET", 0), env_long("T2V_WGRAD_SCAP", 256), getenv("T2V_WGRAD_NOQ") == nullptr,
-                               env_long("T2V_WGRAD_MINCPS", 4), getenv("T2V_NO_WGRAD_THIN") == nullptr};
+                               env_long("T2V_WGRAD_MINCPS", 4), getenv("T2V_NO_WGRAD_THIN") == nullptr,
+                               env_long("T2V_POOL_FWD_DB", 1) != 0, env_long("T2V_POOL_DGRAD_DB", 0) != 0,
+                               env_long("T2V_POOL_DGRAD_SPLIT_BELOW", 576), env_long("T2V_POOL_WGRAD_MINCPS", 4)};
     return t;
 }
-
-struct ConvPlan { int bm, bn, bk; bool fast, vecb; int S; long tiles; bool dstride2; };
 
 // frames the GEMM rows of a member run over: every frame; the even ones (dstride = 2); one parity of y's frames (ydstride = 2)
 static inline int out_frames(const t2v_conv_group& g) {
     if (g.ydstride == 2) return (g.Dy + 1 - g.yoff) / 2;
     return g.dstride == 2 ? (g.D + 1) / 2 : g.D;
 }
+// rows a member brings to a launch: its samples, its input voxels, its GEMM rows (= output voxels)
+static inline long samples(const t2v_conv_group& g) { return g.N; }
+static inline long voxels(const t2v_conv_group& g) { return (long)g.N * g.D * g.H * g.W; }
+static inline long gemm_rows(const t2v_conv_group& g) { return (long)g.N * out_frames(g) * g.H * g.W; }
+
+// tile_start[] of a member table for tiles of `rows_per_tile` rows over rows_of(member) rows each; returns the number of tiles
+static long retile(GroupTable& tab, const t2v_conv_group* groups, int ngroups, int rows_per_tile, long (*rows_of)(const t2v_conv_group&)) {
+    long mt = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        tab.tile_start[i] = (int32_t)mt;
+        mt += (rows_of(groups[i]) + rows_per_tile - 1) / rows_per_tile;
+    }
+    for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) tab.tile_start[i] = (int32_t)mt;
+    return mt;
+}
+
+// what the profile record of a forward / data-gradient launch carries: executed (non-padding-tap) MACs x 2, GEMM rows, most taps
+struct FwdStats { double flops = 0; long rows = 0; int taps = 0; };
+static FwdStats fwd_stats(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, long (*rows_of)(const t2v_conv_group&) = gemm_rows) {
+    FwdStats st;
+    for (int i = 0; i < ngroups; ++i) {
+        st.flops += 2.0 * (double)rows_of(groups[i]) * Cout * Cin * groups[i].ntaps;
+        st.rows += rows_of(groups[i]);
+        if (groups[i].ntaps > st.taps) st.taps = groups[i].ntaps;
+    }
+    return st;
+}
+
+// the split-K pass behind a GEMM launch with S > 1 (timed on its own): sums the S partial tiles of the slab in a fixed order
+static void launch_splitk_reduce(const GroupTable& tab, const float* ws, const float* bias, int S, int Cin, int Cout, int flags,
+                                 const FwdStats& st, hipStream_t s) {
+    long blocks = (tab.out_start[tab.n] + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    ProfScope prof_r(4, 0.0, s, st.rows, Cin, Cout, st.taps, tab.n, S);
+    T2V_LAUNCH_PROF(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tab, ws, bias, S, Cout, flags);
+}
+
 static bool group_ok(const t2v_conv_group& g, bool need_ptrs) {
     if (need_ptrs && (!g.x || !g.y)) return false;
     if (g.dstride < 0 || g.dstride > 2 || g.ydstride < 0 || g.ydstride > 2) return false;
@@ -2666,20 +2713,21 @@ static bool group_ok(const t2v_conv_group& g, bool need_ptrs) {
     return true;
 }
 
+// The GEMM tiling of a forward / data-gradient launch: tile (bm voxels x bn channels, K chunks of bk), the member table on
+// those tiles, and the split-K count S. Base of the fp32 and the bf16 decision (FwdLaunch, Bf16Launch).
+struct ConvPlan { int bm, bn, bk; bool fast, vecb; int S; long tiles; bool dstride2; };
+
 static bool build_table(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, bool need_ptrs, GroupTable& tab,
                         ConvPlan& p) {
     if (!groups || ngroups < 1 || ngroups > T2V_MAX_GROUPS || Cin < 1 || Cout < 1) return false;
-    long Mtot = 0, Mmax = 0;
+    long Mtot = 0;
     int max_chunk_taps = 1;
     p.dstride2 = false;
     for (int i = 0; i < ngroups; ++i) {
         if (!group_ok(groups[i], need_ptrs)) return false;
-        const long Min = (long)groups[i].N * groups[i].D * groups[i].H * groups[i].W;
-        if (Min * (long)(Cin > Cout ? Cin : Cout) >= (1L << 31)) return false;     // 32-bit voxel indices
-        const long M = (long)groups[i].N * out_frames(groups[i]) * groups[i].H * groups[i].W;      // GEMM rows = output voxels
+        if (voxels(groups[i]) * (long)(Cin > Cout ? Cin : Cout) >= (1L << 31)) return false;     // 32-bit voxel indices
         if (groups[i].dstride == 2 || groups[i].ydstride == 2) p.dstride2 = true;
-        Mtot += M;
-        if (M > Mmax) Mmax = M;
+        Mtot += gemm_rows(groups[i]);
         if (groups[i].ntaps > max_chunk_taps) max_chunk_taps = groups[i].ntaps;
     }
     p.bk = (Cin % 64 == 0) ? 64 : (Cin % 32 == 0) ? 32 : 16;
@@ -2692,33 +2740,27 @@ static bool build_table(const t2v_conv_group* groups, int ngroups, int Cin, int 
         p.bm = (t128 >= tun().tile128_min) ? 128 : 64;
         // 256 x 64 tiles, K chunks of 16, one wave = 64 co x 64 m (four accumulator chains, one LDS read per MFMA) for the
         // launches big enough to fill the chip with them (+3-6 % over the 128 x 64 tile there)
-        if (p.fast && (Cin % 16) == 0 && ((Mtot + 255) / 256) * ((Cout + 63) / 64) >= tun().tile256_min) { p.bm = 256; p.bk = 16; }
+        if (p.fast && ((Mtot + 255) / 256) * ((Cout + 63) / 64) >= tun().tile256_min) { p.bm = 256; p.bk = 16; }
         if (p.bk > 32 && p.bm != 256) p.bk = 32;   // two LDS stages: 48 KB (128x64) / 32 KB (64x64) per workgroup
     }
     if (!p.fast) p.bk = 16;
-    long mt = 0, ot = 0;
+    long ot = 0;
     tab.n = ngroups;
     for (int i = 0; i < ngroups; ++i) {
         tab.g[i] = groups[i];
-        const long M = (long)groups[i].N * out_frames(groups[i]) * groups[i].H * groups[i].W;
-        tab.tile_start[i] = (int32_t)mt;
         tab.out_start[i] = ot;
-        mt += (M + p.bm - 1) / p.bm;
-        ot += M * Cout;
+        ot += gemm_rows(groups[i]) * Cout;
     }
-    for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) { tab.tile_start[i] = (int32_t)mt; tab.out_start[i] = ot; }
-    tab.tile_start[ngroups] = (int32_t)mt;
-    tab.out_start[ngroups] = ot;
-    p.tiles = mt * ((Cout + p.bn - 1) / p.bn);
+    for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) tab.out_start[i] = ot;
+    p.tiles = retile(tab, groups, ngroups, p.bm, gemm_rows) * ((Cout + p.bn - 1) / p.bn);
     // split-K: the member with the longest reduction keeps >= 2 chunks per split; members with fewer chunks
     // than splits just leave their surplus splits empty (they write zero partial tiles)
     const long min_chunks = p.fast ? (long)max_chunk_taps * (Cin / p.bk) : ((long)max_chunk_taps * Cin + p.bk - 1) / p.bk;
     long S = 1;
     // a reduction of <= 8 chunks (the 1x1 convolutions up to 256 input channels) is not worth a split: the second launch costs
     // more than the idle CUs (measured: -26 launches, -0.07 ms per iteration)
-    static const long split_target = env_long("T2V_SPLIT_TARGET", 768);      // workgroups a split launch aims at (developer sweeps)
     if (p.tiles < 384 && min_chunks > tun().nosplit_chunks) {
-        S = (split_target + p.tiles - 1) / p.tiles;
+        S = (tun().split_target + p.tiles - 1) / p.tiles;
         long maxS = min_chunks / 2;
         if (S > maxS) S = maxS;
         if (S > 64) S = 64;
@@ -2752,44 +2794,16 @@ static bool strip_ok(const GroupTable& tab) {
 }
 // the fp32 strip kernel gathers x through 32-bit byte offsets (buffer loads)
 static bool strip_fits32(const GroupTable& tab, int Cin) {
-    for (int i = 0; i < tab.n; ++i) {
-        const t2v_conv_group& g = tab.g[i];
-        if ((long)g.N * g.D * g.H * g.W * (long)Cin >= (1L << 30)) return false;
-    }
-    return true;
-}
-
-// Which instantiation a (tile, chunk) choice ends up in: the strip variant (three dx taps from one staged strip) when the
-// members carry their taps in (row, dx) order. Shared by the launcher and by t2v_conv_fwd_plan. (`ks`: K-split wave layout of
-// the plan query's out[6]; always 1 — the two-chains-per-wave form was dropped for the three-taps-per-round kernel.)
-struct ConvVariant { bool strip; int ks; bool s3; };
-static ConvVariant conv_variant(const GroupTable& tab, const ConvPlan& p, int BM, int BN, int BKT, int Cin, int Cout, int flags) {
-    ConvVariant v{false, 1, false};
-    if (p.fast && (BKT == 32 || BM == 256) && (Cin % BKT) == 0 && tun().strip && strip_ok(tab) && strip_fits32(tab, Cin)) {
-        v.strip = true;
-        // tiles with 64 output channels (64 / 128 voxels x 32 channels, 256 voxels x 16 channels): all three dx taps per barrier
-        // round (conv_igemm_strip3_kernel; +12-15 % over one dx per round on every one of them); 128 x 32 keeps the per-dx form
-        v.s3 = BN == 64;
-    }
-    return v;
-}
-
-// The double-buffered form of the 64- and 256-voxel strip3 tiles (conv_igemm_strip3_kernel<64, BKT, 2, true, true>, <256, 16, 1, true,
-// true>): 0 = not taken, else its channels per round (64 voxels: 16 = four workgroups per CU, 32 = two; 256 voxels: 16). Every member
-// must carry all three dx taps and Cout % 4 == 0. T2V_STRIP3_DB (0 / 16 / 32) and T2V_STRIP3_DB256 (0 / 1) override. Shared by the launcher and the plan query (out[3] = channels per round, out[6] = 2).
-static int strip3_db(const GroupTable& tab, const ConvPlan& p) {
-    static const long db = env_long("T2V_STRIP3_DB", 16), db256 = env_long("T2V_STRIP3_DB256", 1);
-    if (!p.vecb || p.bn != 64 || (p.bm != 64 && p.bm != 256)) return 0;
-    if (p.bm == 64 ? (db != 16 && db != 32) : db256 == 0) return 0;
     for (int i = 0; i < tab.n; ++i)
-        if (tab.g[i].dx[0] >= 0) return 0;
-    return p.bm == 64 ? (int)db : 16;              // (the 256-voxel tile: 16-channel rounds, two workgroups per CU as before)
+        if (voxels(tab.g[i]) * (long)Cin >= (1L << 30)) return false;
+    return true;
 }
 
 // Wave quantisation of the 256-voxel tile: the kernel fits 3 workgroups on a CU but runs no faster per CU with 3 than with 2
 // (2 x 255 us = 3 x 382 us per 256 tiles), so a launch of e.g. 1024 tiles (the generator step's D forward, M = 262144) took
 // one round of 768 and a tail of 256 = 692 us where two rounds of 512 take 510. The launcher therefore picks the resident
-// workgroups per CU (2 or 3) that minimises rounds x residents and pads the dynamic LDS request to enforce it.
+// workgroups per CU (2 or 3) that minimises rounds x residents and pads the dynamic LDS request to enforce it. (Needs the
+// device, so it runs at launch time, for the launches whose decision says occ_pad.)
 struct OccInfo { int occ = 0, lds = 0, cus = 0; };
 template <class K>
 static int occupancy_pad(K kernel, OccInfo& info, long nwg) {
@@ -2818,227 +2832,231 @@ static int occupancy_pad(K kernel, OccInfo& info, long nwg) {
     return need > info.lds ? need - info.lds : 0;
 }
 
-template <int BM, int BN, int WAVES_CO, int BKT>
-static void launch_conv_t(const GroupTable& tab, const float* wp, const float* bias, float* slab, int Cin, int Cout, int flags,
-                          const ConvPlan& p, hipStream_t s) {
-    dim3 grid((unsigned)tab.tile_start[tab.n], (unsigned)((Cout + BN - 1) / BN), (unsigned)p.S);
-    const ConvVariant v = conv_variant(tab, p, BM, BN, BKT, Cin, Cout, flags);
-    if (v.s3) {
-        if constexpr (BN == 64 && ((BM != 256 && BKT == 32) || (BM == 256 && BKT == 16))) {
-            constexpr int WCO3 = BM == 256 ? 1 : 2;
-            const long nwg = (long)grid.x * grid.y * grid.z;
-            int pad = 0;
-            if constexpr (BM == 256) {
-                if (strip3_db(tab, p)) {
-                    T2V_LAUNCH_PROF((conv_igemm_strip3_kernel<256, 16, 1, true, true>), grid, dim3(256), 0, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
-                    return;
-                }
-            }
-            if constexpr (BM == 64) {
-                // the double-buffered form (one barrier per round, staging between the MFMAs): every member three taps wide
-                const int db = strip3_db(tab, p);
-                const bool all3 = true;
-                if (db == 32 && all3) {
-                    T2V_LAUNCH_PROF((conv_igemm_strip3_kernel<64, 32, 2, true, true>), grid, dim3(256), 0, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
-                    return;
-                }
-                if (db == 16 && all3) {
-                    T2V_LAUNCH_PROF((conv_igemm_strip3_kernel<64, 16, 2, true, true>), grid, dim3(256), 0, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
-                    return;
-                }
-            }
-            if (p.vecb) {
-                static OccInfo oi;
-                if (BM == 256) pad = occupancy_pad(conv_igemm_strip3_kernel<BM, BKT, WCO3, true>, oi, nwg);
-                T2V_LAUNCH_PROF((conv_igemm_strip3_kernel<BM, BKT, WCO3, true>), grid, dim3(256), pad, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
-            } else {
-                static OccInfo oi;
-                if (BM == 256) pad = occupancy_pad(conv_igemm_strip3_kernel<BM, BKT, WCO3, false>, oi, nwg);
-                T2V_LAUNCH_PROF((conv_igemm_strip3_kernel<BM, BKT, WCO3, false>), grid, dim3(256), pad, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
-            }
-        }
-        return;
+// ------------------------------------------------------------------------------------------------
+// THE decision of a forward / data-gradient launch in fp32: which kernel, on which tiles, over which grid, with how many
+// k-splits and how much workspace. decide_fwd fills it (and the member table the kernels read) from the launch's arguments;
+// t2v_conv_fwd_plan serialises it (fwd_plan_out, also the profile record's plan), t2v_conv_fwd_grouped_ws_floats reads one
+// field and t2v_conv_fwd_grouped switches over `kernel`: change a choice here and all three follow.
+// ------------------------------------------------------------------------------------------------
+enum class FwdKernel {                 // (the values are out[0] of the plan query)
+    Igemm = 0,                         // conv_igemm_kernel: one tap x bk channels per round
+    Strip = 1,                         // conv_igemm_strip_kernel: the 128 x 32 tile, the dx taps of a row from one staged strip
+    Thin = 2,                          // conv_thin_kernel: Cout <= 4, the weight in LDS
+    Linear = 3,                        // linear_thin_kernel: Cout <= 4 on 1x1x1 maps
+    ThinTwoPass = 4,                   // thin_taps[_mfma]_kernel + thin_shift_sum_kernel: Cout = 1 with many taps and voxels
+    Strip3 = 5,                        // conv_igemm_strip3_kernel: tiles of 64 channels, all three dx taps per barrier round
+    Stem = 12                          // conv_stem[_mfma]_kernel: 1 or 3 input channels
+};
+static inline bool is_gemm(FwdKernel k) { return k == FwdKernel::Igemm || k == FwdKernel::Strip || k == FwdKernel::Strip3; }
+struct FwdLaunch : ConvPlan {          // bm, bn, bk, fast, vecb as the plan query reports them; S = 1 for the kernels that never split
+    FwdKernel kernel;
+    int db;                // Strip3: channels per round of the double-buffered form (<64, 16 | 32, 2, true, true>, <256, 16, 1, true, true>); 0: single-stage
+    bool occ_pad;          // Strip3 on 256-voxel tiles, single-stage: occupancy_pad picks the dynamic-LDS pad at launch time
+    int nslots;            // Thin, ThinTwoPass: weight slots the members address
+    dim3 grid, block;
+    bool reduce;           // launch_splitk_reduce follows (S > 1)
+    int64_t ws_floats;     // workspace the launch uses: the split-K slab, or the per-slot products of ThinTwoPass (which falls back to Thin without)
+    bool needs_ws;         // refused without a workspace
+    bool launchable;       // false: frame-strided members on anything but a non-accumulating Strip3 (refused by the launcher, planned anyway)
+    int64_t ws_query;      // what t2v_conv_fwd_grouped_ws_floats answers: ws_floats but for the two quirks in decide_fwd
+};
+
+// The double-buffered form of the 64- and 256-voxel strip3 tiles: 0 = not taken, else its channels per round (64 voxels: 16 = four
+// workgroups per CU, 32 = two; 256 voxels: 16, two workgroups per CU as before). Every member must carry all three dx taps and Cout % 4 == 0.
+static int strip3_db(const GroupTable& tab, const ConvPlan& p) {
+    const long db = tun().strip3_db;
+    if (!p.vecb || p.bn != 64 || (p.bm != 64 && p.bm != 256)) return 0;
+    if (p.bm == 64 ? (db != 16 && db != 32) : !tun().strip3_db256) return 0;
+    for (int i = 0; i < tab.n; ++i)
+        if (tab.g[i].dx[0] >= 0) return 0;
+    return p.bm == 64 ? (int)db : 16;
+}
+
+static bool decide_fwd(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int flags, bool need_ptrs, GroupTable& tab,
+                       FwdLaunch& d) {
+    if (!build_table(groups, ngroups, Cin, Cout, need_ptrs, tab, d)) return false;
+    const int64_t out_floats = tab.out_start[ngroups];
+    const int S_gemm = d.S;
+    // the strip variants of the GEMM tile: the members carry their taps in (row, dx) order. Tiles with 64 output channels take
+    // all three dx taps per barrier round (+12-15 % over one dx per round on every one of them); 128 x 32 keeps the per-dx form
+    const bool strip = d.fast && (d.bk == 32 || d.bm == 256) && (Cin % d.bk) == 0 && tun().strip && strip_ok(tab) && strip_fits32(tab, Cin);
+    const bool strip3 = strip && d.bn == 64;
+    bool one_voxel = Cout <= 4, slot0 = true;         // a Linear layer: 1x1x1 maps with one tap each ... whose weight is slot 0
+    for (int i = 0; i < ngroups; ++i) {
+        one_voxel = one_voxel && groups[i].D == 1 && groups[i].H == 1 && groups[i].W == 1 && groups[i].ntaps == 1;
+        slot0 = slot0 && groups[i].widx[0] == 0;
     }
-    if (v.strip) {
-        if constexpr (BN == 32) {
-            if (p.vecb) T2V_LAUNCH_PROF((conv_igemm_strip_kernel<BM, BN, WAVES_CO, BKT, true>), grid, dim3(256), 0, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
-            else T2V_LAUNCH_PROF((conv_igemm_strip_kernel<BM, BN, WAVES_CO, BKT, false>), grid, dim3(256), 0, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
-        }
-        return;
-    }
-    if (p.fast) {
-        if (p.vecb) T2V_LAUNCH_PROF((conv_igemm_kernel<BM, BN, WAVES_CO, BKT, true, true>), grid, dim3(256), 0, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
-        else T2V_LAUNCH_PROF((conv_igemm_kernel<BM, BN, WAVES_CO, BKT, true, false>), grid, dim3(256), 0, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
+    const bool thin = thin_ok(groups, ngroups, Cin, Cout, d.nslots);
+    d.db = 0;
+    d.block = dim3(256);
+    d.ws_floats = 0;
+    d.launchable = !d.dstride2 || (!thin && !(flags & T2V_CONV_ACCUM) && strip3);
+    if (one_voxel && slot0) {
+        d.kernel = FwdKernel::Linear;
+        d.bm = 0; d.bn = Cout == 1 ? 1 : 4;
+        d.grid = dim3((unsigned)((retile(tab, groups, ngroups, 1, samples) + 3) / 4));      // four samples per workgroup
+    } else if (thin) {
+        const bool two_pass = thin_two_pass(groups, ngroups, Cin, Cout, d.nslots);
+        d.kernel = two_pass ? FwdKernel::ThinTwoPass : FwdKernel::Thin;
+        d.bm = 256; d.bn = Cout == 1 ? 1 : 4;
+        d.grid = dim3((unsigned)retile(tab, groups, ngroups, 256, voxels));
+        if (two_pass) d.ws_floats = (int64_t)d.nslots * out_floats;
+    } else if (stem_ok(groups, ngroups, Cin, Cout, flags)) {
+        d.kernel = FwdKernel::Stem;
+        d.bm = 256; d.bn = Cin;
+        d.grid = dim3((unsigned)retile(tab, groups, ngroups, 256, voxels));
+        if (Cin == 1 && (Cout % 32) == 0) d.block = dim3(512);                              // conv_stem_mfma_kernel
     } else {
-        T2V_LAUNCH_PROF((conv_igemm_kernel<BM, BN, WAVES_CO, 16, false, false>), grid, dim3(256), 0, s, tab, wp, bias, slab, Cin, Cout, flags, p.S);
+        d.kernel = strip3 ? FwdKernel::Strip3 : strip ? FwdKernel::Strip : FwdKernel::Igemm;
+        if (strip3) d.db = strip3_db(tab, d);
+        d.grid = dim3((unsigned)tab.tile_start[ngroups], (unsigned)((Cout + d.bn - 1) / d.bn), (unsigned)d.S);
+        if (d.S > 1) d.ws_floats = (int64_t)d.S * out_floats;
     }
+    if (!is_gemm(d.kernel)) { d.bk = 0; d.fast = d.vecb = false; d.S = 1; }
+    d.occ_pad = d.kernel == FwdKernel::Strip3 && d.bm == 256 && !d.db;
+    d.reduce = d.S > 1;
+    // (as it always was: a Linear launch too wide for the thin kernels' LDS is refused without a workspace where the GEMM tiling
+    // would have split K, although linear_thin_kernel reads none)
+    d.needs_ws = d.reduce || (d.kernel == FwdKernel::Linear && !thin && S_gemm > 1);
+    // Two quirks of the size query, kept as they are (fixing them changes what callers allocate):
+    d.ws_query = d.ws_floats;
+    if (d.kernel == FwdKernel::Stem && S_gemm > 1) d.ws_query = (int64_t)S_gemm * out_floats;    // the split-K slab of the GEMM the stem kernels replace
+    if (is_gemm(d.kernel) && one_voxel) d.ws_query = 0;          // Linear-shaped members whose weight is not slot 0 run (and may split) the GEMM
+    return true;
 }
 
 // Launch-plan query (no launch): the kernel instantiation t2v_conv_fwd_grouped would run for these members.
-// out[0] kind (0 implicit GEMM, 1 strip implicit GEMM, 2 thin conv (Cout <= 4), 3 thin linear, 4 thin two-pass),
-// out[1..3] tile BM, BN and K chunk, out[4] FAST (Cin % 16 == 0), out[5] VECB (Cout % 4 == 0), out[6] KS, out[7] split-K S.
+// out[0] kind (FwdKernel), out[1..3] tile BM, BN and K chunk (the channels per round of a double-buffered strip3),
+// out[4] FAST (Cin % 16 == 0), out[5] VECB (Cout % 4 == 0), out[6] 2 for the double-buffered forms, 1 for the other GEMMs, out[7] split-K S.
 // Used by the parity tests to assert that every instantiation — in particular the ones the benchmark shapes select —
 // is reached by at least one checked case.
-static void fill_fwd_plan(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int flags, const GroupTable& tab,
-                          const ConvPlan& p, int32_t* out) {
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    int nslots;
-    bool pure_linear = Cout <= 4;
-    for (int i = 0; i < ngroups; ++i)
-        pure_linear = pure_linear && groups[i].D == 1 && groups[i].H == 1 && groups[i].W == 1 && groups[i].ntaps == 1 && groups[i].widx[0] == 0;
-    if (pure_linear) { out[0] = 3; out[2] = Cout == 1 ? 1 : 4; out[7] = 1; return; }
-    if (thin_ok(groups, ngroups, Cin, Cout, nslots)) {
-        out[0] = thin_two_pass(groups, ngroups, Cin, Cout, nslots) ? 4 : 2;
-        out[1] = 256; out[2] = Cout == 1 ? 1 : 4; out[7] = 1;
-        return;
-    }
-    if (stem_ok(groups, ngroups, Cin, Cout, flags)) { out[0] = 12; out[1] = 256; out[2] = Cin; out[7] = 1; return; }      // conv_stem_kernel<Cin>
-    const int bk = (p.bm == 256 && p.bn == 64) ? 16 : (p.bk == 32 ? 32 : 16);
-    const ConvVariant v = conv_variant(tab, p, p.bm, p.bn, bk, Cin, Cout, flags);
-    out[0] = v.s3 ? 5 : (v.strip ? 1 : 0);
-    out[1] = p.bm; out[2] = p.bn; out[3] = p.fast ? bk : 16;
-    out[4] = p.fast ? 1 : 0; out[5] = (p.fast && p.vecb) ? 1 : 0; out[6] = v.ks; out[7] = p.S;
-    if (v.s3 && (bk == 32 || p.bm == 256)) {
-        const int db = strip3_db(tab, p);
-        if (db) { out[3] = db; out[6] = 2; }
-    }
+static void fwd_plan_out(const FwdLaunch& d, int32_t* out) {
+    const int32_t v[8] = {(int32_t)d.kernel, d.bm, d.bn, d.db ? d.db : d.bk, d.fast ? 1 : 0, (d.fast && d.vecb) ? 1 : 0,
+                          is_gemm(d.kernel) ? (d.db ? 2 : 1) : 0, d.S};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
 }
 extern "C" int t2v_conv_fwd_plan(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int flags, int32_t* out) {
     GroupTable tab;
-    ConvPlan p;
-    if (!out || !build_table(groups, ngroups, Cin, Cout, false, tab, p)) return T2V_EINVAL;
-    fill_fwd_plan(groups, ngroups, Cin, Cout, flags, tab, p, out);
+    FwdLaunch d;
+    if (!out || !decide_fwd(groups, ngroups, Cin, Cout, flags, false, tab, d)) return T2V_EINVAL;
+    fwd_plan_out(d, out);
     return T2V_OK;
 }
-
 extern "C" int64_t t2v_conv_fwd_grouped_ws_floats(const t2v_conv_group* groups, int ngroups, int Cin, int Cout) {
     GroupTable tab;
-    ConvPlan p;
-    if (!build_table(groups, ngroups, Cin, Cout, false, tab, p)) return T2V_EINVAL;
-    int nslots;
-    if (thin_ok(groups, ngroups, Cin, Cout, nslots))
-        return thin_two_pass(groups, ngroups, Cin, Cout, nslots) ? (int64_t)nslots * tab.out_start[ngroups] : 0;
-    if (Cout <= 4) {
-        bool pl = true;
-        for (int i = 0; i < ngroups; ++i) pl = pl && groups[i].D == 1 && groups[i].H == 1 && groups[i].W == 1 && groups[i].ntaps == 1;
-        if (pl) return 0;
+    FwdLaunch d;
+    if (!decide_fwd(groups, ngroups, Cin, Cout, 0, false, tab, d)) return T2V_EINVAL;
+    return d.ws_query;
+}
+
+// the GEMM kernels of one tile: which of its instantiations the decision names
+template <int BM, int BN, int WAVES_CO, int BKT>
+static void launch_gemm_tile(const FwdLaunch& d, const GroupTable& tab, const float* wp, const float* bias, float* slab, int Cin,
+                             int Cout, int flags, hipStream_t s) {
+#define GEMM_LAUNCH(kernel, pad) T2V_LAUNCH_PROF(kernel, d.grid, d.block, pad, s, tab, wp, bias, slab, Cin, Cout, flags, d.S)
+    switch (d.kernel) {
+    case FwdKernel::Strip3:
+        if constexpr (BN == 64 && ((BM != 256 && BKT == 32) || (BM == 256 && BKT == 16))) {
+            constexpr int WCO3 = BM == 256 ? 1 : 2;
+            const long nwg = (long)d.grid.x * d.grid.y * d.grid.z;
+            // the double-buffered forms: one barrier per round, staging between the MFMAs
+            if constexpr (BM == 256) {
+                if (d.db) { GEMM_LAUNCH((conv_igemm_strip3_kernel<256, 16, 1, true, true>), 0); return; }
+            }
+            if constexpr (BM == 64) {
+                if (d.db == 32) { GEMM_LAUNCH((conv_igemm_strip3_kernel<64, 32, 2, true, true>), 0); return; }
+                if (d.db == 16) { GEMM_LAUNCH((conv_igemm_strip3_kernel<64, 16, 2, true, true>), 0); return; }
+            }
+            if (d.vecb) {
+                static OccInfo oi;
+                GEMM_LAUNCH((conv_igemm_strip3_kernel<BM, BKT, WCO3, true>), d.occ_pad ? occupancy_pad(conv_igemm_strip3_kernel<BM, BKT, WCO3, true>, oi, nwg) : 0);
+            } else {
+                static OccInfo oi;
+                GEMM_LAUNCH((conv_igemm_strip3_kernel<BM, BKT, WCO3, false>), d.occ_pad ? occupancy_pad(conv_igemm_strip3_kernel<BM, BKT, WCO3, false>, oi, nwg) : 0);
+            }
+        }
+        return;
+    case FwdKernel::Strip:
+        if constexpr (BN == 32) {
+            if (d.vecb) GEMM_LAUNCH((conv_igemm_strip_kernel<BM, BN, WAVES_CO, BKT, true>), 0);
+            else GEMM_LAUNCH((conv_igemm_strip_kernel<BM, BN, WAVES_CO, BKT, false>), 0);
+        }
+        return;
+    default:
+        if (!d.fast) GEMM_LAUNCH((conv_igemm_kernel<BM, BN, WAVES_CO, 16, false, false>), 0);
+        else if (d.vecb) GEMM_LAUNCH((conv_igemm_kernel<BM, BN, WAVES_CO, BKT, true, true>), 0);
+        else GEMM_LAUNCH((conv_igemm_kernel<BM, BN, WAVES_CO, BKT, true, false>), 0);
     }
-    return p.S > 1 ? (int64_t)p.S * tab.out_start[ngroups] : 0;
+#undef GEMM_LAUNCH
 }
 
 extern "C" int t2v_conv_fwd_grouped(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, const float* wp,
                                     const float* bias, float* ws, int flags, void* stream) {
     GroupTable tab;
-    ConvPlan p;
-    if (!wp || !build_table(groups, ngroups, Cin, Cout, true, tab, p)) return T2V_EINVAL;
+    FwdLaunch d;
+    if (!wp || !decide_fwd(groups, ngroups, Cin, Cout, flags, true, tab, d)) return T2V_EINVAL;
     if (flags & T2V_CONV_MASK_OUT) {
         if (flags & T2V_CONV_ACCUM) return T2V_EINVAL;
         for (int i = 0; i < ngroups; ++i)
             if (!groups[i].mask) return T2V_EINVAL;
     }
+    if ((d.needs_ws && !ws) || !d.launchable) return T2V_EINVAL;
     hipStream_t s = (hipStream_t)stream;
 #ifdef T2V_ABLATION
     if (const char* e = getenv("T2V_DEBUG_FLAGS")) flags |= atoi(e);     // developer ablations (wrong results)
 #endif
-    int nslots;
-    const bool thin = thin_ok(groups, ngroups, Cin, Cout, nslots);
-    if (!thin && p.S > 1 && !ws && !stem_ok(groups, ngroups, Cin, Cout, flags)) return T2V_EINVAL;
-    if (p.dstride2) {                      // frame-strided outputs: the three-taps-per-round strip kernels only
-        if (thin || (flags & T2V_CONV_ACCUM)) return T2V_EINVAL;
-        bool s3 = false;
-        if (p.bn == 64 && p.bm == 256) s3 = conv_variant(tab, p, 256, 64, 16, Cin, Cout, flags).s3;
-        else if (p.bn == 64 && p.bk == 32) s3 = conv_variant(tab, p, p.bm, 64, 32, Cin, Cout, flags).s3;
-        if (!s3) return T2V_EINVAL;
-    }
-    double flops = 0;
-    for (int i = 0; i < ngroups; ++i)
-        flops += 2.0 * (double)groups[i].N * out_frames(groups[i]) * groups[i].H * groups[i].W * Cout * Cin * groups[i].ntaps;
-    long Mtot_ = 0;
-    int taps_ = 0;
-    for (int i = 0; i < ngroups; ++i) {
-        Mtot_ += (long)groups[i].N * out_frames(groups[i]) * groups[i].H * groups[i].W;
-        if (groups[i].ntaps > taps_) taps_ = groups[i].ntaps;
-    }
+    const FwdStats st = fwd_stats(groups, ngroups, Cin, Cout);
+    const int taps = d.kernel == FwdKernel::Linear ? 1 : st.taps;
     int32_t plan_[8];
-    fill_fwd_plan(groups, ngroups, Cin, Cout, flags, tab, p, plan_);
-    bool pure_linear = Cout <= 4;
-    for (int i = 0; i < ngroups; ++i)
-        pure_linear = pure_linear && groups[i].D == 1 && groups[i].H == 1 && groups[i].W == 1 && groups[i].ntaps == 1 && groups[i].widx[0] == 0;
-    if (pure_linear) {
-        long rows = 0;
-        for (int i = 0; i < ngroups; ++i) { tab.tile_start[i] = (int32_t)rows; rows += groups[i].N; }
-        for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) tab.tile_start[i] = (int32_t)rows;
-        ProfScope prof(3, flops, s, Mtot_, Cin, Cout, 1, ngroups, 1);
+    fwd_plan_out(d, plan_);
+    FwdKernel kernel = d.kernel;
+    if (kernel == FwdKernel::ThinTwoPass && !ws) kernel = FwdKernel::Thin;      // no workspace: the one-pass kernel
+    {
+        ProfScope prof(is_gemm(kernel) ? 0 : 3, st.flops, s, st.rows, Cin, Cout, taps, ngroups, d.S);
         ProfScope::set_plan(plan_, 8);
-        if (Cout == 1) T2V_LAUNCH_PROF(linear_thin_kernel<1>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, tab, wp, bias, Cin, Cout, flags);
-        else T2V_LAUNCH_PROF(linear_thin_kernel<4>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, tab, wp, bias, Cin, Cout, flags);
-        return launch_status();
-    }
-    if (thin) {
-        // re-tile for 256 voxels per workgroup
-        long mt = 0;
-        for (int i = 0; i < ngroups; ++i) {
-            tab.tile_start[i] = (int32_t)mt;
-            mt += ((long)groups[i].N * groups[i].D * groups[i].H * groups[i].W + 255) / 256;
-        }
-        for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) tab.tile_start[i] = (int32_t)mt;
-        if (ws && thin_two_pass(groups, ngroups, Cin, Cout, nslots)) {
-            {
-                ProfScope prof(3, flops, s, Mtot_, Cin, Cout, taps_, ngroups, 1);
-                ProfScope::set_plan(plan_, 8);
-                if (Cin == 64) T2V_LAUNCH_PROF(thin_taps_mfma_kernel<32>, dim3((unsigned)mt), dim3(512), 0, s, tab, wp, ws, nslots, flags);
-                else if (Cin == 32) T2V_LAUNCH_PROF(thin_taps_mfma_kernel<16>, dim3((unsigned)mt), dim3(512), 0, s, tab, wp, ws, nslots, flags);
-                else if (Cin == 16) T2V_LAUNCH_PROF(thin_taps_mfma_kernel<8>, dim3((unsigned)mt), dim3(512), 0, s, tab, wp, ws, nslots, flags);
-                else if (Cin == 128) T2V_LAUNCH_PROF(thin_taps_mfma_kernel<64>, dim3((unsigned)mt), dim3(512), 0, s, tab, wp, ws, nslots, flags);
-                else T2V_LAUNCH_PROF(thin_taps_kernel, dim3((unsigned)mt), dim3(256), 0, s, tab, wp, ws, Cin, nslots, flags);
+        switch (kernel) {
+        case FwdKernel::Linear:
+            if (Cout == 1) T2V_LAUNCH_PROF(linear_thin_kernel<1>, d.grid, d.block, 0, s, tab, wp, bias, Cin, Cout, flags);
+            else T2V_LAUNCH_PROF(linear_thin_kernel<4>, d.grid, d.block, 0, s, tab, wp, bias, Cin, Cout, flags);
+            break;
+        case FwdKernel::Thin:
+            if (Cout == 1) T2V_LAUNCH_PROF(conv_thin_kernel<1>, d.grid, d.block, 0, s, tab, wp, bias, Cin, Cout, d.nslots, flags);
+            else T2V_LAUNCH_PROF(conv_thin_kernel<4>, d.grid, d.block, 0, s, tab, wp, bias, Cin, Cout, d.nslots, flags);
+            break;
+        case FwdKernel::ThinTwoPass:
+            if (Cin == 64) T2V_LAUNCH_PROF(thin_taps_mfma_kernel<32>, d.grid, dim3(512), 0, s, tab, wp, ws, d.nslots, flags);
+            else if (Cin == 32) T2V_LAUNCH_PROF(thin_taps_mfma_kernel<16>, d.grid, dim3(512), 0, s, tab, wp, ws, d.nslots, flags);
+            else if (Cin == 16) T2V_LAUNCH_PROF(thin_taps_mfma_kernel<8>, d.grid, dim3(512), 0, s, tab, wp, ws, d.nslots, flags);
+            else if (Cin == 128) T2V_LAUNCH_PROF(thin_taps_mfma_kernel<64>, d.grid, dim3(512), 0, s, tab, wp, ws, d.nslots, flags);
+            else T2V_LAUNCH_PROF(thin_taps_kernel, d.grid, d.block, 0, s, tab, wp, ws, Cin, d.nslots, flags);
+            break;
+        case FwdKernel::Stem:
+            if (Cin == 1 && (Cout % 32) == 0) T2V_LAUNCH_PROF(conv_stem_mfma_kernel, d.grid, d.block, 0, s, tab, wp, bias, Cout, flags);
+            else if (Cin == 1) T2V_LAUNCH_PROF(conv_stem_kernel<1>, d.grid, d.block, 0, s, tab, wp, bias, Cout, flags);
+            else T2V_LAUNCH_PROF(conv_stem_kernel<3>, d.grid, d.block, 0, s, tab, wp, bias, Cout, flags);
+            break;
+        default:
+            if (d.bn == 32) {
+                if (d.bk == 32) launch_gemm_tile<128, 32, 1, 32>(d, tab, wp, bias, ws, Cin, Cout, flags, s);
+                else launch_gemm_tile<128, 32, 1, 16>(d, tab, wp, bias, ws, Cin, Cout, flags, s);
+            } else if (d.bm == 256) {
+                launch_gemm_tile<256, 64, 1, 16>(d, tab, wp, bias, ws, Cin, Cout, flags, s);
+            } else if (d.bm == 128) {
+                if (d.bk == 32) launch_gemm_tile<128, 64, 2, 32>(d, tab, wp, bias, ws, Cin, Cout, flags, s);
+                else launch_gemm_tile<128, 64, 2, 16>(d, tab, wp, bias, ws, Cin, Cout, flags, s);
+            } else {
+                if (d.bk == 32) launch_gemm_tile<64, 64, 2, 32>(d, tab, wp, bias, ws, Cin, Cout, flags, s);
+                else launch_gemm_tile<64, 64, 2, 16>(d, tab, wp, bias, ws, Cin, Cout, flags, s);
             }
-            ProfScope prof2(3, 0.0, s, Mtot_, Cin, Cout, taps_, ngroups, 2);
-            T2V_LAUNCH_PROF(thin_shift_sum_kernel, dim3((unsigned)mt), dim3(256), 0, s, tab, ws, bias, nslots, flags);
-            return launch_status();
         }
-        ProfScope prof(3, flops, s, Mtot_, Cin, Cout, taps_, ngroups, 1);
-        ProfScope::set_plan(plan_, 8);
-        if (Cout == 1) T2V_LAUNCH_PROF(conv_thin_kernel<1>, dim3((unsigned)mt), dim3(256), 0, s, tab, wp, bias, Cin, Cout, nslots, flags);
-        else T2V_LAUNCH_PROF(conv_thin_kernel<4>, dim3((unsigned)mt), dim3(256), 0, s, tab, wp, bias, Cin, Cout, nslots, flags);
-        return launch_status();
     }
-    if (stem_ok(groups, ngroups, Cin, Cout, flags)) {
-        long mt = 0;
-        for (int i = 0; i < ngroups; ++i) {
-            tab.tile_start[i] = (int32_t)mt;
-            mt += ((long)groups[i].N * groups[i].D * groups[i].H * groups[i].W + 255) / 256;
-        }
-        for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) tab.tile_start[i] = (int32_t)mt;
-        ProfScope prof(3, flops, s, Mtot_, Cin, Cout, taps_, ngroups, 1);
-        ProfScope::set_plan(plan_, 8);
-        if (Cin == 1 && (Cout % 32) == 0) T2V_LAUNCH_PROF(conv_stem_mfma_kernel, dim3((unsigned)mt), dim3(512), 0, s, tab, wp, bias, Cout, flags);
-        else if (Cin == 1) T2V_LAUNCH_PROF(conv_stem_kernel<1>, dim3((unsigned)mt), dim3(256), 0, s, tab, wp, bias, Cout, flags);
-        else T2V_LAUNCH_PROF(conv_stem_kernel<3>, dim3((unsigned)mt), dim3(256), 0, s, tab, wp, bias, Cout, flags);
-        return launch_status();
+    if (kernel == FwdKernel::ThinTwoPass) {
+        ProfScope prof2(3, 0.0, s, st.rows, Cin, Cout, taps, ngroups, 2);
+        T2V_LAUNCH_PROF(thin_shift_sum_kernel, d.grid, d.block, 0, s, tab, ws, bias, d.nslots, flags);
     }
-    ProfScope prof(0, flops, s, Mtot_, Cin, Cout, taps_, ngroups, p.S);      // executed (non-padding-tap) MACs x 2
-    ProfScope::set_plan(plan_, 8);
-    const int bk = p.bk;
-    if (p.bn == 32) {
-        if (bk == 32) launch_conv_t<128, 32, 1, 32>(tab, wp, bias, ws, Cin, Cout, flags, p, s);
-        else launch_conv_t<128, 32, 1, 16>(tab, wp, bias, ws, Cin, Cout, flags, p, s);
-    } else if (p.bm == 256) {
-        launch_conv_t<256, 64, 1, 16>(tab, wp, bias, ws, Cin, Cout, flags, p, s);
-    } else if (p.bm == 128) {
-        if (bk == 32) launch_conv_t<128, 64, 2, 32>(tab, wp, bias, ws, Cin, Cout, flags, p, s);
-        else launch_conv_t<128, 64, 2, 16>(tab, wp, bias, ws, Cin, Cout, flags, p, s);
-    } else {
-        if (bk == 32) launch_conv_t<64, 64, 2, 32>(tab, wp, bias, ws, Cin, Cout, flags, p, s);
-        else launch_conv_t<64, 64, 2, 16>(tab, wp, bias, ws, Cin, Cout, flags, p, s);
-    }
-    int st = launch_status();
-    if (st) return st;
-    if (p.S > 1) {
-        long blocks = (tab.out_start[ngroups] + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        ProfScope prof_r(4, 0.0, s, Mtot_, Cin, Cout, taps_, ngroups, p.S);     // the split-K pass, timed on its own
-        T2V_LAUNCH_PROF(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tab, ws, bias, p.S, Cout, flags);
-    }
+    int st_ = launch_status();
+    if (st_ || !d.reduce) return st_;
+    launch_splitk_reduce(tab, ws, bias, d.S, Cin, Cout, flags, st, s);
     return launch_status();
 }
 
@@ -3052,87 +3070,78 @@ extern "C" int t2v_conv_fwd_grouped_bf16_ok(const t2v_conv_group* groups, int ng
     if ((Cin % 32) != 0 || Cout <= 4 || thin_ok(groups, ngroups, Cin, Cout, nslots)) return 0;
     return 1;
 }
-// Which bf16 instantiation a launch lands on (shared by the launcher and by t2v_conv_fwd_bf16_plan): same tiling decisions as
-// the fp32 path, restricted to the tiles the bf16 kernels have (128 x 64, 64 x 64) — re-tiled when build_table picked 128 x 32
-// (Cout <= 32) or 256 x 64. kind: 6 plain implicit GEMM (1-wide kernels, W = 1 members, tensors beyond 32-bit byte offsets),
-// 8 strip3 (three dx taps per barrier round).
-struct Bf16Variant { int kind; int bm; };
-static bool bf16_variant(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int flags, GroupTable& tab, ConvPlan& p, Bf16Variant& v) {
-    if (p.bn != 64 || p.bm == 256) {
-        long mt = 0;
-        p.bn = 64;
-        p.bm = 128;
-        for (int i = 0; i < ngroups; ++i) {
-            const long M = (long)groups[i].N * out_frames(groups[i]) * groups[i].H * groups[i].W;
-            tab.tile_start[i] = (int32_t)mt;
-            mt += (M + p.bm - 1) / p.bm;
-        }
-        for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) tab.tile_start[i] = (int32_t)mt;
+// The decision of a bf16 launch (shared by the launcher and by t2v_conv_fwd_bf16_plan): same tiling decisions as the fp32 path,
+// restricted to the tiles the bf16 kernels have (128 x 64, 64 x 64) — re-tiled when build_table picked 128 x 32 (Cout <= 32) or
+// 256 x 64; K chunks of 32. False where the bf16 entry point refuses the launch (the caller then uses fp32).
+enum class Bf16Kernel {
+    Igemm = 6,        // conv_igemm_bf16_kernel: 1-wide kernels, W = 1 members, tensors beyond 32-bit byte offsets
+    Strip3 = 8        // conv_igemm_bf16_strip3_kernel: three dx taps per barrier round
+};
+struct Bf16Launch : ConvPlan {
+    Bf16Kernel kernel;
+    dim3 grid, block;
+    bool reduce;      // launch_splitk_reduce follows (S > 1); the launch needs a workspace of S x output floats then
+};
+static bool decide_bf16(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int flags, bool need_ptrs, GroupTable& tab,
+                        Bf16Launch& d) {
+    if (!t2v_conv_fwd_grouped_bf16_ok(groups, ngroups, Cin, Cout) || !build_table(groups, ngroups, Cin, Cout, need_ptrs, tab, d)) return false;
+    if (d.bn != 64 || d.bm == 256) {
+        d.bn = 64;
+        d.bm = 128;
+        retile(tab, groups, ngroups, d.bm, gemm_rows);
     }
+    d.bk = 32;
     const long wbytes = 2L * T2V_MAX_TAPS * Cout * Cin;                            // (32-bit byte offsets into the packed weight)
-    const bool s3_b16 = tun().strip && strip_ok(tab) && strip_fits32(tab, Cin) && wbytes < (1L << 31);
-    if (p.dstride2 && (!s3_b16 || (flags & T2V_CONV_ACCUM))) return false;        // frame-strided members: strip3 form only
-    v.bm = p.bm == 128 ? 128 : 64;
-    v.kind = s3_b16 ? 8 : 6;
+    const bool strip3 = tun().strip && strip_ok(tab) && strip_fits32(tab, Cin) && wbytes < (1L << 31);
+    if (d.dstride2 && (!strip3 || (flags & T2V_CONV_ACCUM))) return false;        // frame-strided members: strip3 form only
+    d.kernel = strip3 ? Bf16Kernel::Strip3 : Bf16Kernel::Igemm;
+    d.grid = dim3((unsigned)tab.tile_start[ngroups], (unsigned)((Cout + 63) / 64), (unsigned)d.S);
+    d.block = dim3(256);
+    d.reduce = d.S > 1;
     return true;
 }
-// Launch-plan query of the bf16-compute entry point (no launch; host arithmetic): out[0] kind (6 conv_igemm_bf16_kernel,
-// 8 conv_igemm_bf16_strip3_kernel), out[1] BM (128 / 64), out[2] BN = 64, out[3] K chunk = 32, out[4] 1 for frame-strided members
-// (dstride / ydstride), out[7] split-K S; the rest 0. T2V_EINVAL where t2v_conv_fwd_grouped_bf16 would refuse the launch (the caller then uses fp32).
+// Launch-plan query of the bf16-compute entry point (no launch; host arithmetic): out[0] kind (Bf16Kernel), out[1] BM (128 / 64),
+// out[2] BN = 64, out[3] K chunk = 32, out[4] 1 for frame-strided members (dstride / ydstride), out[7] split-K S; the rest 0.
+// T2V_EINVAL where t2v_conv_fwd_grouped_bf16 would refuse the launch (the caller then uses fp32).
+static void bf16_plan_out(const Bf16Launch& d, int32_t* out) {
+    const int32_t v[8] = {(int32_t)d.kernel, d.bm, d.bn, d.bk, d.dstride2 ? 1 : 0, 0, 0, d.S};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+}
 extern "C" int t2v_conv_fwd_bf16_plan(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int flags, int32_t* out) {
     GroupTable tab;
-    ConvPlan p;
-    Bf16Variant v;
-    if (!out || !t2v_conv_fwd_grouped_bf16_ok(groups, ngroups, Cin, Cout) || !build_table(groups, ngroups, Cin, Cout, false, tab, p) ||
-        !bf16_variant(groups, ngroups, Cin, Cout, flags, tab, p, v))
-        return T2V_EINVAL;
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    out[0] = v.kind; out[1] = v.bm; out[2] = 64; out[3] = 32; out[4] = p.dstride2 ? 1 : 0; out[7] = p.S;
+    Bf16Launch d;
+    if (!out || !decide_bf16(groups, ngroups, Cin, Cout, flags, false, tab, d)) return T2V_EINVAL;
+    bf16_plan_out(d, out);
     return T2V_OK;
 }
 extern "C" int t2v_conv_fwd_grouped_bf16(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, const void* wpb,
                                          const float* bias, float* ws, int flags, void* stream) {
     GroupTable tab;
-    ConvPlan p;
-    if (!wpb || !t2v_conv_fwd_grouped_bf16_ok(groups, ngroups, Cin, Cout) || !build_table(groups, ngroups, Cin, Cout, true, tab, p))
-        return T2V_EINVAL;
+    Bf16Launch d;
+    if (!wpb || !decide_bf16(groups, ngroups, Cin, Cout, flags, true, tab, d)) return T2V_EINVAL;
     if (flags & T2V_CONV_MASK_OUT) {
         if (flags & T2V_CONV_ACCUM) return T2V_EINVAL;
         for (int i = 0; i < ngroups; ++i)
             if (!groups[i].mask) return T2V_EINVAL;
     }
-    Bf16Variant v;
-    if (!bf16_variant(groups, ngroups, Cin, Cout, flags, tab, p, v)) return T2V_EINVAL;
-    if (p.S > 1 && !ws) return T2V_EINVAL;
+    if (d.reduce && !ws) return T2V_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    double flops = 0;
-    long Mtot_ = 0;
-    int taps_ = 0;
-    for (int i = 0; i < ngroups; ++i) {
-        const long M = (long)groups[i].N * out_frames(groups[i]) * groups[i].H * groups[i].W;
-        flops += 2.0 * (double)M * Cout * Cin * groups[i].ntaps;
-        Mtot_ += M;
-        if (groups[i].ntaps > taps_) taps_ = groups[i].ntaps;
-    }
+    const FwdStats st = fwd_stats(groups, ngroups, Cin, Cout);
+    const __bf16* w = (const __bf16*)wpb;
     {
-        ProfScope prof(5, flops, s, Mtot_, Cin, Cout, taps_, ngroups, p.S);
-        int32_t plan_[8] = {v.kind, v.bm, 64, 32, p.dstride2 ? 1 : 0, 0, 0, p.S};
+        ProfScope prof(5, st.flops, s, st.rows, Cin, Cout, st.taps, ngroups, d.S);
+        int32_t plan_[8];
+        bf16_plan_out(d, plan_);
         ProfScope::set_plan(plan_, 8);
-        dim3 grid((unsigned)tab.tile_start[tab.n], (unsigned)((Cout + 63) / 64), (unsigned)p.S);
-        if (v.kind == 8) {
-            if (v.bm == 128) T2V_LAUNCH_PROF(conv_igemm_bf16_strip3_kernel<128>, grid, dim3(256), 0, s, tab, (const __bf16*)wpb, bias, ws, Cin, Cout, flags, p.S);
-            else T2V_LAUNCH_PROF(conv_igemm_bf16_strip3_kernel<64>, grid, dim3(256), 0, s, tab, (const __bf16*)wpb, bias, ws, Cin, Cout, flags, p.S);
-        } else if (v.bm == 128) T2V_LAUNCH_PROF(conv_igemm_bf16_kernel<128>, grid, dim3(256), 0, s, tab, (const __bf16*)wpb, bias, ws, Cin, Cout, flags, p.S);
-        else T2V_LAUNCH_PROF(conv_igemm_bf16_kernel<64>, grid, dim3(256), 0, s, tab, (const __bf16*)wpb, bias, ws, Cin, Cout, flags, p.S);
+        if (d.kernel == Bf16Kernel::Strip3) {
+            if (d.bm == 128) T2V_LAUNCH_PROF(conv_igemm_bf16_strip3_kernel<128>, d.grid, d.block, 0, s, tab, w, bias, ws, Cin, Cout, flags, d.S);
+            else T2V_LAUNCH_PROF(conv_igemm_bf16_strip3_kernel<64>, d.grid, d.block, 0, s, tab, w, bias, ws, Cin, Cout, flags, d.S);
+        } else if (d.bm == 128) T2V_LAUNCH_PROF(conv_igemm_bf16_kernel<128>, d.grid, d.block, 0, s, tab, w, bias, ws, Cin, Cout, flags, d.S);
+        else T2V_LAUNCH_PROF(conv_igemm_bf16_kernel<64>, d.grid, d.block, 0, s, tab, w, bias, ws, Cin, Cout, flags, d.S);
     }
-    int st = launch_status();
-    if (st) return st;
-    if (p.S > 1) {
-        long blocks = (tab.out_start[ngroups] + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        ProfScope prof_r(4, 0.0, s, Mtot_, Cin, Cout, taps_, ngroups, p.S);
-        T2V_LAUNCH_PROF(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tab, ws, bias, p.S, Cout, flags);
-    }
+    int st_ = launch_status();
+    if (st_ || !d.reduce) return st_;
+    launch_splitk_reduce(tab, ws, bias, d.S, Cin, Cout, flags, st, s);
     return launch_status();
 }
 
@@ -4556,171 +4565,212 @@ __global__ __launch_bounds__(256) void conv_wgrad_gemm_kernel(const WGroupTable 
     }
 }
 
-struct WgradPlan { int S, cps; uint32_t live; int nlive; long nchunks; bool rows3; uint32_t liverows; int nrows; bool strided; bool gemm; bool thin; };
+// ------------------------------------------------------------------------------------------------
+// THE decision of a weight-gradient launch (un-pooled: decide_wgrad, pooled: decide_pool_wgrad): kernel, grid, k-splits and the
+// layout of the slab of partial sums. The plan queries serialise it (wgrad_plan_out, also the profile record's plan), the slab
+// queries read slab_floats / bias_floats, the launchers switch over `kernel`, wgrad_finish reads which reduce follows.
+// ------------------------------------------------------------------------------------------------
+enum class WgradKernel {               // (the values are out[0] of the plan queries)
+    Taps = 0,                          // conv_wgrad_kernel / conv_wgrad_bf16_kernel: per-tap 64 x 64 tiles
+    Cols = 1,                          // conv_wgrad_cols_kernel: (tap, ci) column tiles for Cin < 64
+    Rows3 = 2,                         // conv_wgrad3_kernel<bf16>: the three dx taps of a kernel row share a workgroup
+    Gemm = 3,                          // conv_wgrad_gemm_kernel: the TN product on 1x1x1 maps
+    Thin = 4,                          // conv_wgrad_thin_kernel: the streaming kernel for narrow inputs
+    PoolRows3 = 11                     // conv_pool_wgrad_kernel
+};
+struct WgradLaunch {
+    WgradKernel kernel;
+    bool bf16;                         // T2V_CONV_BF16 and a kernel that has a bf16-compute form (Taps, Rows3)
+    bool strided;                      // dL/dy on the even frames (dstride = 2)
+    int S, cps;                        // k-splits, 32-voxel chunks per split
+    long nchunks;
+    uint32_t live, liverows;           // taps / kernel rows (dz, dy) at least one member can touch
+    int nlive, nrows;                  // slab slots (Rows3: 3 per live row, dead dx taps are written as zeros), live rows
+    dim3 grid, block;                  // grid.z = S
+    bool reduce_small;                 // wgrad_reduce_small_kernel (small weight, many splits), else wgrad_reduce_kernel
+    int64_t slab_floats, bias_floats;  // the S x slots x Cout x Cin partial sums, and the S x Cout bias side-sums behind them
+};
 
-static bool build_wtable(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int kH, int kW, bool need_ptrs,
-                         WGroupTable& tab, WgradPlan& p) {
+// k-splits of a launch of `base` workgroups per split over nch chunks, at least min_cps chunks per split.
+// Workgroups to aim at: the kernels run 4 workgroups per CU, 1024 resident at a time. WHOLE rounds of them are what counts
+// (measured on the stem layer, 8 ragged members: 1024 -> 732 us, 1536 -> 837, 2048 -> 743, 3072 -> 735; the same picture on the
+// mid-size and the generator's layers), so ONE round: the fewest k-splits, i.e. the smallest slab (50 instead of 113 MB on the
+// stem) and half the reduce time, at the same or a better kernel time.
+// (768 instead of 1024 — a quarter less slab — was worth 0.02 ms on the benchmark's pyramid launches and cost the full-clip D pass
+// 0.2 ms: its weight-gradient launches want whole rounds, 3.26 vs 3.05 ms; the default stays)
+static long wgrad_ksplit(long base, long nch, long min_cps) {
+    const long wg_target = tun().wgrad_target ? tun().wgrad_target : 1024;
+    long S = base >= 1024 ? 1 : (wg_target + base - 1) / base;      // (the tiles of a big weight fill the chip on their own)
+    // at least 4 chunks (128 voxels) per split (8 -> 4: -0.10 ms per iteration, the ~25 small launches are latency chains; pooled:
+    // -0.04 ms once the kernel ran four workgroups per CU)
+    const long maxS = (nch + min_cps - 1) / min_cps;
+    if (S > maxS) S = maxS;
+    if (S < 1) S = 1;
+    if (S > tun().wgrad_scap) S = tun().wgrad_scap;
+    // wave quantisation: 1024 workgroups are resident at a time; a last round that is under a fifth full (2052 = 2 x 1024 + 4)
+    // costs most of a round for little work: give those workgroups' chunks to the full rounds instead
+    const long rounds = (base * S) / 1024, tail = (base * S) % 1024;
+    if (tun().wgrad_quantise && rounds >= 1 && tail > 0 && tail * 5 <= 1024 && (rounds * 1024) / base >= 1) S = (rounds * 1024) / base;
+    return S;
+}
+// chunks per split and the splits that are not empty, the grid's z, the reduce and the slab sizes: the end of both decisions
+static void wgrad_set_splits(WgradLaunch& d, long S, int cps_multiple, int Cin, int Cout) {
+    const long cps = ((d.nchunks + S - 1) / S + cps_multiple - 1) / cps_multiple * cps_multiple;
+    d.cps = (int)cps;
+    d.S = (int)((d.nchunks + cps - 1) / cps);
+    d.grid.z = (unsigned)d.S;
+    d.block = dim3(256);
+    d.reduce_small = (long)Cout * Cin <= 16384 && d.S >= 16;
+    d.slab_floats = (int64_t)d.S * d.nlive * Cout * Cin;
+    d.bias_floats = (int64_t)d.S * Cout;           // every weight-gradient kernel sums the dL/dy tiles it stages on the side
+}
+
+static bool decide_wgrad(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int kH, int kW, int flags, bool need_ptrs,
+                         WGroupTable& tab, WgradLaunch& d) {
     if (!groups || ngroups < 1 || ngroups > T2V_MAX_GROUPS || Cin < 1 || Cout < 1) return false;
     if ((kD != 1 && kD != 3) || (kH != 1 && kH != 3) || (kW != 1 && kW != 3)) return false;
     long nch = 0, maxMC = 0;
-    bool strided = false;
-    p.live = 0;
+    bool strided = false, anyw = false, all1 = true;
+    d.live = 0;
     tab.n = ngroups;
     for (int i = 0; i < ngroups; ++i) {
         const t2v_conv_group& g = groups[i];
         if (need_ptrs && (!g.x || !g.y)) return false;
         if (g.N < 1 || g.D < 1 || g.H < 1 || g.W < 1 || g.dstride < 0 || g.dstride > 2 || g.ydstride > 1 || g.ydstride < 0) return false;
         if (g.dstride == 2) strided = true;          // dL/dy lives on the even frames only ([N,Cout,ceil(D/2),H,W]): 3-tap-row kernel only
-        const long M = (long)g.N * g.D * g.H * g.W;
-        if (M * (long)(Cin > Cout ? Cin : Cout) >= (1L << 30)) return false;     // the gathers use 32-bit BYTE offsets (buffer loads)
-        if (M * (long)(Cin > Cout ? Cin : Cout) > maxMC) maxMC = M * (long)(Cin > Cout ? Cin : Cout);
+        const long MC = voxels(g) * (long)(Cin > Cout ? Cin : Cout);
+        if (MC >= (1L << 30)) return false;          // the gathers use 32-bit BYTE offsets (buffer loads)
+        if (MC > maxMC) maxMC = MC;
+        anyw = anyw || g.W > 1;
+        all1 = all1 && g.D == 1 && g.H == 1 && g.W == 1;
         tab.g[i] = g;
         tab.chunk_start[i] = (int32_t)nch;
-        nch += ((long)g.N * out_frames(g) * g.H * g.W + WG_BK - 1) / WG_BK;       // chunks run over the voxels of dL/dy
+        nch += (gemm_rows(g) + WG_BK - 1) / WG_BK;   // chunks run over the voxels of dL/dy
         for (int a = 0; a < kD; ++a) for (int b = 0; b < kH; ++b) for (int c = 0; c < kW; ++c) {
             const int dz = a - kD / 2, dy = b - kH / 2, dx = c - kW / 2;
-            if (!((g.D == 1 && dz) || (g.H == 1 && dy) || (g.W == 1 && dx))) p.live |= 1u << ((a * kH + b) * kW + c);
+            if (!((g.D == 1 && dz) || (g.H == 1 && dy) || (g.W == 1 && dx))) d.live |= 1u << ((a * kH + b) * kW + c);
         }
     }
     for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) tab.chunk_start[i] = (int32_t)nch;
-    p.nchunks = nch;
-    p.nlive = __builtin_popcount(p.live);
-    // kW == 3 with at least one member wider than one voxel: the three dx taps of a kernel row share a workgroup
-    bool anyw = false;
-    for (int i = 0; i < ngroups; ++i) anyw = anyw || groups[i].W > 1;
-    p.rows3 = (kW == 3) && anyw && Cin >= 64 && maxMC < (1L << 30);   // the 3-tap kernel gathers through 32-bit byte offsets
-    // every member on a 1x1x1 map (only the centre tap lives): the TN-product kernel
-    bool all1 = true;
-    for (int i = 0; i < ngroups; ++i) all1 = all1 && groups[i].D == 1 && groups[i].H == 1 && groups[i].W == 1;
-    p.gemm = all1 && !strided && Cin >= 64 && (Cin % 4) == 0 && (Cout % 4) == 0;
-    if (strided && !p.rows3) return false;
-    p.strided = strided;
-    p.liverows = 0;
+    d.nchunks = nch;
+    d.nlive = __builtin_popcount(d.live);
+    d.strided = strided;
+    d.liverows = 0;
     for (int r = 0; r < kD * kH; ++r)
-        if ((p.live >> (r * kW)) & 7u) p.liverows |= 1u << r;
-    p.nrows = __builtin_popcount(p.liverows);
-    if (p.rows3) p.nlive = p.nrows * 3;            // slab slots (dead dx taps of a live row are written as zeros)
-    // narrow inputs: every (live tap, ci) column fits ONE 32-column tile with a spare column for the bias sums (conv_wgrad_thin_kernel)
-    p.thin = !p.rows3 && !p.gemm && !strided && Cin < 64 && (long)p.nlive * Cin <= 31 && tun().wgrad_thin;
-    if (p.thin) {
-        // a stream over dL/dy: three workgroups per CU (LDS) in ONE round, rounds of 128 voxels (4 chunks), at least 2 rounds per split
-        const long tiles = (Cout + 63) / 64;
-        long S = (768 + tiles - 1) / tiles;
+        if ((d.live >> (r * kW)) & 7u) d.liverows |= 1u << r;
+    d.nrows = __builtin_popcount(d.liverows);
+    const long co_tiles = (Cout + 63) / 64, tiles = co_tiles * ((Cin + 63) / 64);
+    // kW == 3 with at least one member wider than one voxel: the three dx taps of a kernel row share a workgroup
+    // (the 3-tap kernel gathers through 32-bit byte offsets)
+    const bool rows3 = (kW == 3) && anyw && Cin >= 64 && maxMC < (1L << 30);
+    if (strided && !rows3) return false;
+    if (all1 && !strided && Cin >= 64 && (Cin % 4) == 0 && (Cout % 4) == 0) {
+        // every member on a 1x1x1 map (only the centre tap lives). 128 x 128 tiles, one per CU: k-splits only until the chip is
+        // covered once, at least 4 chunks (128 rows) per split. (bf16-compute mode too: the fp32 TN product beats the voxel-major
+        // bf16 per-tap kernel here)
+        d.kernel = WgradKernel::Gemm;
+        const long t128 = (long)((Cout + 127) / 128) * ((Cin + 127) / 128);
+        d.grid = dim3((unsigned)t128);
+        long S = t128 >= 192 ? 1 : (256 + t128 - 1) / t128;
+        const long maxS = (nch + 3) / 4;
+        if (S > maxS) S = maxS;
+        if (S < 1) S = 1;
+        if (S > tun().wgrad_scap) S = tun().wgrad_scap;
+        wgrad_set_splits(d, S, 1, Cin, Cout);
+    } else if (rows3) {
+        d.kernel = WgradKernel::Rows3;
+        d.nlive = d.nrows * 3;
+        d.grid = dim3((unsigned)tiles, (unsigned)d.nrows);
+    } else if (Cin < 64 && (long)d.nlive * Cin <= 31 && tun().wgrad_thin) {
+        // narrow inputs: every (live tap, ci) column fits ONE 32-column tile with a spare column for the bias sums. A stream over
+        // dL/dy: three workgroups per CU (LDS) in ONE round, rounds of 128 voxels (4 chunks), at least 2 rounds per split
+        d.kernel = WgradKernel::Thin;
+        d.grid = dim3((unsigned)co_tiles);
+        long S = (768 + co_tiles - 1) / co_tiles;
         const long maxS = (nch + 7) / 8;
         if (S > maxS) S = maxS;
         if (S < 1) S = 1;
         if (S > 1024) S = 1024;
-        long cps = (nch + S - 1) / S;
-        cps = (cps + 3) / 4 * 4;                  // whole rounds
-        p.cps = (int)cps;
-        p.S = (int)((nch + cps - 1) / cps);
-        return true;
+        wgrad_set_splits(d, S, 4, Cin, Cout);      // whole rounds
+    } else if (Cin < 64) {
+        d.kernel = WgradKernel::Cols;
+        d.grid = dim3((unsigned)(co_tiles * (((long)d.nlive * Cin + 63) / 64)));
+    } else {
+        d.kernel = WgradKernel::Taps;              // grid.y runs over the taps at least one member can touch; the reduce writes the others as zeros
+        d.grid = dim3((unsigned)tiles, (unsigned)d.nlive);
     }
-    if (p.gemm) {                                 // 128 x 128 tiles, one per CU: k-splits only until the chip is covered once
-        const long tiles = (long)((Cout + 127) / 128) * ((Cin + 127) / 128);
-        long S = tiles >= 192 ? 1 : (256 + tiles - 1) / tiles;
-        const long maxS = (nch + 3) / 4;          // at least 4 chunks (128 rows) per split
-        if (S > maxS) S = maxS;
-        if (S < 1) S = 1;
-        if (S > tun().wgrad_scap) S = tun().wgrad_scap;
-        p.cps = (int)((nch + S - 1) / S);
-        p.S = (int)((nch + p.cps - 1) / p.cps);
-        return true;
-    }
-    const long base = p.rows3 ? (long)((Cout + 63) / 64) * ((Cin + 63) / 64) * p.nrows
-                    : (Cin < 64) ? (long)((Cout + 63) / 64) * (((long)p.nlive * Cin + 63) / 64)
-                                 : (long)((Cout + 63) / 64) * ((Cin + 63) / 64) * p.nlive;
-    // workgroups to aim at: the kernels run 4 workgroups per CU, 1024 resident at a time. WHOLE rounds of them are what counts
-    // (measured on the stem layer, 8 ragged members: 1024 -> 732 us, 1536 -> 837, 2048 -> 743, 3072 -> 735; the same picture on the
-    // mid-size and the generator's layers), so ONE round: the fewest k-splits, i.e. the smallest slab (50 instead of 113 MB on the
-    // stem) and half the reduce time, at the same or a better kernel time.
-    const long wg_env = tun().wgrad_target, s_cap = tun().wgrad_scap;
-    // (768 instead of 1024 — a quarter less slab — was worth 0.02 ms on the benchmark's pyramid launches and cost the full-clip D pass
-    // 0.2 ms: its weight-gradient launches want whole rounds, 3.26 vs 3.05 ms; the default stays)
-    const long wg_target = wg_env ? wg_env : 1024;
-    long S = base >= 1024 ? 1 : (wg_target + base - 1) / base;      // (the tiles of a big weight fill the chip on their own)
-    const long mincps = tun().wgrad_min_cps > 0 ? tun().wgrad_min_cps : 8;
-    long maxS = (nch + mincps - 1) / mincps;      // at least 4 chunks (128 voxels) per split (8 -> 4: -0.10 ms per iteration, the ~25 small launches are latency chains)
-    if (S > maxS) S = maxS;
-    if (S < 1) S = 1;
-    if (S > s_cap) S = s_cap;
-    // wave quantisation: 1024 workgroups are resident at a time; a last round that is under a fifth full (2052 = 2 x 1024 + 4)
-    // costs most of a round for little work: give those workgroups' chunks to the full rounds instead
-    const bool no_q = !tun().wgrad_quantise;
-    const long rounds = (base * S) / 1024, tail = (base * S) % 1024;
-    if (!no_q && rounds >= 1 && tail > 0 && tail * 5 <= 1024 && (rounds * 1024) / base >= 1) S = (rounds * 1024) / base;
-    p.cps = (int)((nch + S - 1) / S);
-    p.S = (int)((nch + p.cps - 1) / p.cps);
+    if (d.kernel != WgradKernel::Gemm && d.kernel != WgradKernel::Thin)
+        wgrad_set_splits(d, wgrad_ksplit((long)d.grid.x * d.grid.y, nch, tun().wgrad_min_cps > 0 ? tun().wgrad_min_cps : 8), 1, Cin, Cout);
+    d.bf16 = (flags & T2V_CONV_BF16) && (d.kernel == WgradKernel::Rows3 || d.kernel == WgradKernel::Taps);
     return true;
 }
 
-extern "C" int64_t t2v_conv_wgrad_grouped_slab_floats(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD,
-                                                      int kH, int kW) {
-    WGroupTable tab;
-    WgradPlan p;
-    if (!build_wtable(groups, ngroups, Cin, Cout, kD, kH, kW, false, tab, p)) return T2V_EINVAL;
-    return (int64_t)p.S * p.nlive * Cout * Cin;
-}
-
-// Launch-plan query (no launch) for t2v_conv_wgrad_grouped[_bias]: out[0] kernel (0 per-tap 64x64 tiles, 1 (tap, ci) column
-// tiles for Cin < 64, 2 three-tap kernel rows, 3 the TN product on 1x1x1 maps, 4 the narrow-input streaming kernel), out[1] k-splits S, out[2] 32-voxel chunks per split, out[3] slab slots,
-// out[4] reduce kernel (0 per-64-pairs, 1 the many-splits small-weight form), out[5] workgroups of the main launch.
-static void fill_wgrad_plan(int Cin, int Cout, const WgradPlan& p, int32_t* out) {
-    const long tiles = (long)((Cout + 63) / 64) * ((Cin + 63) / 64);
-    out[0] = p.gemm ? 3 : p.rows3 ? 2 : p.thin ? 4 : (Cin < 64 ? 1 : 0);
-    out[1] = p.S;
-    out[2] = p.cps;
-    out[3] = p.nlive;
-    out[4] = ((long)Cout * Cin <= 16384 && p.S >= 16) ? 1 : 0;
-    if (p.gemm) { out[5] = (int32_t)((long)((Cout + 127) / 128) * ((Cin + 127) / 128) * p.S); return; }
-    if (p.thin) { out[5] = (int32_t)((long)((Cout + 63) / 64) * p.S); return; }
-    out[5] = (int32_t)((p.rows3 ? tiles * p.nrows : Cin < 64 ? (long)((Cout + 63) / 64) * (((long)p.nlive * Cin + 63) / 64)
-                                                              : tiles * p.nlive) * p.S);
+// Launch-plan query (no launch) for t2v_conv_wgrad_grouped[_bias] and the pooled weight gradient: out[0] kernel (WgradKernel),
+// out[1] k-splits S, out[2] 32-voxel chunks per split, out[3] slab slots, out[4] reduce kernel (0 per-64-pairs, 1 the many-splits
+// small-weight form), out[5] workgroups of the main launch; the profile record adds out[6] bf16-compute kernel, out[7] dL/dy on the even frames.
+static void wgrad_plan_out(const WgradLaunch& d, int32_t* out, int n) {
+    const int32_t v[8] = {(int32_t)d.kernel, d.S, d.cps, d.nlive, d.reduce_small ? 1 : 0, (int32_t)((long)d.grid.x * d.grid.y * d.grid.z),
+                          d.bf16 ? 1 : 0, d.strided ? 1 : 0};
+    for (int i = 0; i < n; ++i) out[i] = v[i];
 }
 extern "C" int t2v_conv_wgrad_plan(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int kH, int kW,
                                    int32_t* out) {
     WGroupTable tab;
-    WgradPlan p;
-    if (!out || !build_wtable(groups, ngroups, Cin, Cout, kD, kH, kW, false, tab, p)) return T2V_EINVAL;
-    fill_wgrad_plan(Cin, Cout, p, out);
+    WgradLaunch d;
+    if (!out || !decide_wgrad(groups, ngroups, Cin, Cout, kD, kH, kW, 0, false, tab, d)) return T2V_EINVAL;
+    wgrad_plan_out(d, out, 6);
     return T2V_OK;
 }
-
-extern "C" int64_t t2v_channel_sum_grouped_ws_floats(const t2v_conv_group* groups, int ngroups, int C);
-extern "C" int t2v_channel_sum_grouped(const t2v_conv_group* groups, int ngroups, int C, float* out, float* ws, int accum, void* stream);
-
-// floats the bias part needs behind the weight-gradient slab: S x Cout partial sums (every weight-gradient kernel sums the
-// dL/dy tiles it stages on the side)
-static int64_t wgrad_bias_extra(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, const WgradPlan& p) {
-    return (int64_t)p.S * Cout;
+extern "C" int64_t t2v_conv_wgrad_grouped_slab_floats(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD,
+                                                      int kH, int kW) {
+    WGroupTable tab;
+    WgradLaunch d;
+    if (!decide_wgrad(groups, ngroups, Cin, Cout, kD, kH, kW, 0, false, tab, d)) return T2V_EINVAL;
+    return d.slab_floats;
 }
 extern "C" int64_t t2v_conv_wgrad_grouped_bias_slab_floats(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD,
                                                            int kH, int kW) {
     WGroupTable tab;
-    WgradPlan p;
-    if (!build_wtable(groups, ngroups, Cin, Cout, kD, kH, kW, false, tab, p)) return T2V_EINVAL;
-    return (int64_t)p.S * p.nlive * Cout * Cin + wgrad_bias_extra(groups, ngroups, Cin, Cout, p);
+    WgradLaunch d;
+    if (!decide_wgrad(groups, ngroups, Cin, Cout, kD, kH, kW, 0, false, tab, d)) return T2V_EINVAL;
+    return d.slab_floats + d.bias_floats;
 }
 
-static int wgrad_impl(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int kH, int kW, float* dw,
-                      float* dbias, float* slab, int flags, void* stream, t2v_wgrad_src* out_src = nullptr);
-extern "C" int t2v_conv_wgrad_grouped(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int kH, int kW,
-                                      float* dw, float* slab, int flags, void* stream) {
-    return wgrad_impl(groups, ngroups, Cin, Cout, kD, kH, kW, dw, nullptr, slab, flags, stream);
+// What follows the main launch of a weight gradient (un-pooled and pooled): describe the partial sums for the deferred reduce
+// (out_src; t2v_wgrad_reduce_multi), or sum them now — the bias side-sums by one workgroup of the same reduce. `map`: original
+// tap -> slab slot or -1, `bias_part`: the side-sums behind the slab, null when no bias gradient is wanted.
+static int wgrad_finish(const WgradLaunch& d, int T, const TapMap& map, float* slab, const float* bias_part, float* dw, float* dbias,
+                        int Cin, int Cout, int flags, hipStream_t s, t2v_wgrad_src* out_src) {
+    const long CoCi = (long)Cout * Cin;
+    if (out_src) {
+        out_src->slab = slab;
+        out_src->bias_slab = bias_part;
+        out_src->ntaps = d.nlive;
+        out_src->S = d.S;
+        out_src->tap_stride = CoCi;
+        out_src->split_stride = (int64_t)d.nlive * CoCi;
+        for (int t = 0; t < T2V_MAX_TAPS; ++t) out_src->map[t] = (int8_t)(t < T ? map.j[t] : -1);
+        return T2V_OK;
+    }
+    const int accum = (flags & T2V_CONV_ACCUM) ? 1 : 0, accum_bias = (flags & T2V_CONV_ACCUM_BIAS) ? 1 : 0;
+    ProfScope prof2(2, 0.0, s, CoCi, Cin, Cout, T, d.nlive, d.S);
+    if (d.reduce_small)
+        T2V_LAUNCH_PROF(wgrad_reduce_small_kernel, dim3((unsigned)((CoCi + 63) / 64), (unsigned)T), dim3(256), 0, s, slab, dw, CoCi, T,
+                   d.nlive, d.S, map, accum, bias_part, dbias, Cout, accum_bias);
+    else
+        T2V_LAUNCH_PROF(wgrad_reduce_kernel, dim3((unsigned)((CoCi + 63) / 64)), dim3(256), 0, s, slab, dw, CoCi, T, d.nlive, d.S, map,
+                   accum, bias_part, dbias, Cout, accum_bias);
+    return launch_status();
 }
-extern "C" int t2v_conv_wgrad_grouped_bias(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int kH, int kW,
-                                           float* dw, float* dbias, float* slab, int flags, void* stream) {
-    if (!dbias) return T2V_EINVAL;
-    return wgrad_impl(groups, ngroups, Cin, Cout, kD, kH, kW, dw, dbias, slab, flags, stream);
-}
+
+// dw / dbias null with out_src: the deferred form (want_bias says whether the bias side-sums are wanted)
 static int wgrad_impl(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int kH, int kW, float* dw,
-                      float* dbias, float* slab, int flags, void* stream, t2v_wgrad_src* out_src) {
+                      float* dbias, bool want_bias, float* slab, int flags, void* stream, t2v_wgrad_src* out_src) {
     WGroupTable tab;
-    WgradPlan p;
-    if ((!dw && !out_src) || !slab || !build_wtable(groups, ngroups, Cin, Cout, kD, kH, kW, true, tab, p)) return T2V_EINVAL;
+    WgradLaunch d;
+    if ((!dw && !out_src) || !slab || !decide_wgrad(groups, ngroups, Cin, Cout, kD, kH, kW, flags, true, tab, d)) return T2V_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* bias_part = slab + (size_t)p.S * p.nlive * Cout * Cin;         // behind the weight-gradient slab
-    const bool bias_fused = true;                                         // all three weight-gradient kernels sum dL/dy on the side
+    float* bias_part = want_bias ? slab + d.slab_floats : (float*)nullptr;        // behind the weight-gradient slab
 #ifdef T2V_ABLATION
     if (const char* e = getenv("T2V_DEBUG_FLAGS")) flags |= atoi(e);     // developer ablations (wrong results)
 #endif
@@ -4735,16 +4785,15 @@ static int wgrad_impl(const t2v_conv_group* groups, int ngroups, int Cin, int Co
     LiveRows lrows;
     lrows.n = 0;
     for (int r = 0; r < 9; ++r) lrows.r[r] = 0;
-    if (p.rows3) {
+    if (d.kernel == WgradKernel::Rows3) {
         for (int r = 0; r < kD * kH; ++r)
-            if ((p.liverows >> r) & 1u) {
+            if ((d.liverows >> r) & 1u) {
                 for (int c = 0; c < 3; ++c) map.j[r * 3 + c] = lrows.n * 3 + c;
                 lrows.r[lrows.n++] = (int8_t)r;
             }
-        live.n = lrows.n * 3;
     } else {
         for (int t = 0; t < T; ++t)
-            if ((p.live >> t) & 1u) { map.j[t] = live.n; live.t[live.n++] = (int8_t)t; }
+            if ((d.live >> t) & 1u) { map.j[t] = live.n; live.t[live.n++] = (int8_t)t; }
     }
     double flops = 0;
     for (int i = 0; i < ngroups; ++i) {
@@ -4753,69 +4802,44 @@ static int wgrad_impl(const t2v_conv_group* groups, int ngroups, int Cin, int Co
             const int dz = a - kD / 2, dy = b - kH / 2, dx = c - kW / 2;
             if (!((groups[i].D == 1 && dz) || (groups[i].H == 1 && dy) || (groups[i].W == 1 && dx))) ++live_g;
         }
-        flops += 2.0 * (double)groups[i].N * out_frames(groups[i]) * groups[i].H * groups[i].W * Cout * Cin * live_g;
+        flops += 2.0 * (double)gemm_rows(groups[i]) * Cout * Cin * live_g;
     }
-    // grid.y runs over the taps at least one member can touch; the others are written as zeros by the reduce
     {
-        ProfScope prof(1, flops, s, p.nchunks * WG_BK, Cin, Cout, live.n, ngroups, p.S);
-        int32_t plan_[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-        fill_wgrad_plan(Cin, Cout, p, plan_);
-        plan_[6] = ((flags & T2V_CONV_BF16) && !p.gemm && (p.rows3 || Cin >= 64)) ? 1 : 0;   // conv_wgrad3_kernel<true> / conv_wgrad_bf16_kernel
-        plan_[7] = p.strided ? 1 : 0;                                                  // dL/dy on the even frames (dstride = 2)
+        ProfScope prof(1, flops, s, d.nchunks * WG_BK, Cin, Cout, d.nlive, ngroups, d.S);
+        int32_t plan_[8];
+        wgrad_plan_out(d, plan_, 8);
         ProfScope::set_plan(plan_, 8);
-        if (p.gemm) {                          // (bf16-compute mode too: the fp32 TN product beats the voxel-major bf16 per-tap kernel here)
-            dim3 grid((unsigned)(((Cout + 127) / 128) * ((Cin + 127) / 128)), 1u, (unsigned)p.S);
-            T2V_LAUNCH_PROF(conv_wgrad_gemm_kernel, grid, dim3(256), 0, s, tab, slab, Cin, Cout, flags, p.cps,
-                            dbias ? bias_part : (float*)nullptr);
-        } else if (p.rows3) {
-            dim3 grid((unsigned)(((Cout + 63) / 64) * ((Cin + 63) / 64)), (unsigned)lrows.n, (unsigned)p.S);
-            if (flags & T2V_CONV_BF16)
-                T2V_LAUNCH_PROF(conv_wgrad3_kernel<true>, grid, dim3(256), 0, s, tab, slab, Cin, Cout, kD, kH, flags, p.cps, lrows,
-                                dbias ? bias_part : (float*)nullptr);
-            else
-                T2V_LAUNCH_PROF(conv_wgrad3_kernel<false>, grid, dim3(256), 0, s, tab, slab, Cin, Cout, kD, kH, flags, p.cps, lrows,
-                                dbias ? bias_part : (float*)nullptr);
-        } else if (Cin < 64 && p.thin) {
-            dim3 grid((unsigned)((Cout + 63) / 64), 1u, (unsigned)p.S);
-            T2V_LAUNCH_PROF(conv_wgrad_thin_kernel, grid, dim3(256), 0, s, tab, slab, Cin, Cout, T, kH, kW, flags, p.cps, live,
-                            dbias ? bias_part : (float*)nullptr);
-        } else if (Cin < 64) {
-            dim3 grid((unsigned)(((Cout + 63) / 64) * ((live.n * Cin + 63) / 64)), 1u, (unsigned)p.S);
-            T2V_LAUNCH_PROF(conv_wgrad_cols_kernel, grid, dim3(256), 0, s, tab, slab, Cin, Cout, T, kH, kW, flags, p.cps, live,
-                            dbias ? bias_part : (float*)nullptr);
-        } else {
-            dim3 grid((unsigned)(((Cout + 63) / 64) * ((Cin + 63) / 64)), (unsigned)live.n, (unsigned)p.S);
-            if (flags & T2V_CONV_BF16)
-                T2V_LAUNCH_PROF(conv_wgrad_bf16_kernel, grid, dim3(256), 0, s, tab, slab, Cin, Cout, T, kH, kW, flags, p.cps, live,
-                                dbias ? bias_part : (float*)nullptr);
-            else
-                T2V_LAUNCH_PROF(conv_wgrad_kernel, grid, dim3(256), 0, s, tab, slab, Cin, Cout, T, kH, kW, flags, p.cps, live,
-                                dbias ? bias_part : (float*)nullptr);
+        switch (d.kernel) {
+        case WgradKernel::Gemm:
+            T2V_LAUNCH_PROF(conv_wgrad_gemm_kernel, d.grid, d.block, 0, s, tab, slab, Cin, Cout, flags, d.cps, bias_part);
+            break;
+        case WgradKernel::Rows3:
+            if (d.bf16) T2V_LAUNCH_PROF(conv_wgrad3_kernel<true>, d.grid, d.block, 0, s, tab, slab, Cin, Cout, kD, kH, flags, d.cps, lrows, bias_part);
+            else T2V_LAUNCH_PROF(conv_wgrad3_kernel<false>, d.grid, d.block, 0, s, tab, slab, Cin, Cout, kD, kH, flags, d.cps, lrows, bias_part);
+            break;
+        case WgradKernel::Thin:
+            T2V_LAUNCH_PROF(conv_wgrad_thin_kernel, d.grid, d.block, 0, s, tab, slab, Cin, Cout, T, kH, kW, flags, d.cps, live, bias_part);
+            break;
+        case WgradKernel::Cols:
+            T2V_LAUNCH_PROF(conv_wgrad_cols_kernel, d.grid, d.block, 0, s, tab, slab, Cin, Cout, T, kH, kW, flags, d.cps, live, bias_part);
+            break;
+        default:
+            if (d.bf16) T2V_LAUNCH_PROF(conv_wgrad_bf16_kernel, d.grid, d.block, 0, s, tab, slab, Cin, Cout, T, kH, kW, flags, d.cps, live, bias_part);
+            else T2V_LAUNCH_PROF(conv_wgrad_kernel, d.grid, d.block, 0, s, tab, slab, Cin, Cout, T, kH, kW, flags, d.cps, live, bias_part);
         }
     }
     int st = launch_status();
     if (st) return st;
-    if (out_src) {                  // deferred reduce (t2v_wgrad_reduce_multi): describe the partial sums instead of summing them
-        out_src->slab = slab;
-        out_src->bias_slab = (dbias && bias_fused) ? bias_part : (const float*)nullptr;
-        out_src->ntaps = live.n;
-        out_src->S = p.S;
-        out_src->tap_stride = (int64_t)Cout * Cin;
-        out_src->split_stride = (int64_t)live.n * Cout * Cin;
-        for (int t = 0; t < T2V_MAX_TAPS; ++t) out_src->map[t] = (int8_t)(t < T ? map.j[t] : -1);
-        return T2V_OK;
-    }
-    const float* bias_in = (dbias && bias_fused) ? bias_part : (const float*)nullptr;   // summed by one workgroup of the reduce below
-    const int accum_bias = (flags & T2V_CONV_ACCUM_BIAS) ? 1 : 0;
-    const long CoCi = (long)Cout * Cin;
-    ProfScope prof2(2, 0.0, s, CoCi, Cin, Cout, T, live.n, p.S);
-    if (CoCi <= 16384 && p.S >= 16)
-        T2V_LAUNCH_PROF(wgrad_reduce_small_kernel, dim3((unsigned)((CoCi + 63) / 64), (unsigned)T), dim3(256), 0, s, slab, dw, CoCi, T,
-                   live.n, p.S, map, (flags & T2V_CONV_ACCUM) ? 1 : 0, bias_in, dbias, Cout, accum_bias);
-    else
-        T2V_LAUNCH_PROF(wgrad_reduce_kernel, dim3((unsigned)((CoCi + 63) / 64)), dim3(256), 0, s, slab, dw, CoCi, T, live.n, p.S, map,
-                   (flags & T2V_CONV_ACCUM) ? 1 : 0, bias_in, dbias, Cout, accum_bias);
-    return launch_status();
+    return wgrad_finish(d, T, map, slab, bias_part, dw, dbias, Cin, Cout, flags, s, out_src);
+}
+extern "C" int t2v_conv_wgrad_grouped(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int kH, int kW,
+                                      float* dw, float* slab, int flags, void* stream) {
+    return wgrad_impl(groups, ngroups, Cin, Cout, kD, kH, kW, dw, nullptr, false, slab, flags, stream, nullptr);
+}
+extern "C" int t2v_conv_wgrad_grouped_bias(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int kH, int kW,
+                                           float* dw, float* dbias, float* slab, int flags, void* stream) {
+    if (!dbias) return T2V_EINVAL;
+    return wgrad_impl(groups, ngroups, Cin, Cout, kD, kH, kW, dw, dbias, true, slab, flags, stream, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4830,17 +4854,24 @@ extern "C" int t2v_conv_wgrad_grouped_partial(const t2v_conv_group* groups, int 
                                               int kW, float* slab, int want_bias, int flags, t2v_wgrad_src* out_src,
                                               void* stream) {
     if (!out_src) return T2V_EINVAL;
-    WGroupTable tab;
-    WgradPlan p;
-    if (!build_wtable(groups, ngroups, Cin, Cout, kD, kH, kW, false, tab, p)) return T2V_EINVAL;
-    float dummy;                                                    // (non-null marker: the bias side-sums are wanted)
-    return wgrad_impl(groups, ngroups, Cin, Cout, kD, kH, kW, nullptr, want_bias ? &dummy : nullptr, slab, flags, stream, out_src);
+    return wgrad_impl(groups, ngroups, Cin, Cout, kD, kH, kW, nullptr, nullptr, want_bias != 0, slab, flags, stream, out_src);
 }
 // ------------------------------------------------------------------------------------------------
 // Pooled convolution: host side (kernels: conv_pool_fwd_kernel, conv_pool_dgrad_kernel, conv_pool_wgrad_kernel; the
-// pointwise halves t2v_pool_boxsum / t2v_pool_unbox live in pointwise.hip).
+// pointwise halves t2v_pool_boxsum / t2v_pool_unbox live in pointwise.hip). One decision per launch here too: PoolLaunch for
+// the forward and the data gradient (decide_pool_fwd, decide_pool_dgrad), WgradLaunch for the weight gradient
+// (decide_pool_wgrad); t2v_pool_conv_plan and the size queries read them, the launchers run them.
 // ------------------------------------------------------------------------------------------------
-struct PoolPlan { int S; long tiles; bool vecb; };
+enum class PoolKernel { Fwd = 9, Dgrad = 10 };       // conv_pool_fwd_kernel<64, db>, conv_pool_dgrad_kernel<db> (the values: out[0] of the plan query)
+struct PoolLaunch {
+    PoolKernel kernel;
+    bool db;               // the double-buffered form: 16-channel rounds (else 32), KS 2 in the plan
+    bool vecb;
+    int S;                 // k-splits: the forward's go through launch_splitk_reduce, the data gradient's are plane sets t2v_pool_unbox sums
+    long tiles;
+    dim3 grid, block;
+    int64_t ws_floats;     // forward: the split-K slab
+};
 static bool pool_member_ok(const t2v_conv_group& g, bool need_ptrs) {
     if (need_ptrs && (!g.x || !g.y)) return false;
     if (g.N < 1 || g.H < 2 || g.W < 2 || (g.H & 1) || (g.W & 1)) return false;
@@ -4851,11 +4882,12 @@ static bool pool_member_ok(const t2v_conv_group& g, bool need_ptrs) {
 static inline long pool_rows(const t2v_conv_group& g) { return (long)g.N * (g.dstride ? g.D / 2 : 1) * (g.H / 2) * (g.W / 2); }
 static inline long pool_padded(const t2v_conv_group& g) { return (long)(g.dstride ? g.D + 1 : 1) * (g.H + 1) * (g.W + 2); }
 static inline long pool_grid(const t2v_conv_group& g) { return (long)(g.dstride ? g.D / 2 + 1 : 1) * (g.H / 2 + 1) * (g.W / 2 + 1); }
+static inline long pool_grid_rows(const t2v_conv_group& g) { return (long)g.N * pool_grid(g); }
 
 // forward: rows = pooled voxels, 64-voxel x 64-channel tiles, rounds of (kernel row, 32 channels)
-static bool build_pool_fwd(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, bool need_ptrs, GroupTable& tab, PoolPlan& p) {
+static bool decide_pool_fwd(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, bool need_ptrs, GroupTable& tab, PoolLaunch& d) {
     if (!groups || ngroups < 1 || ngroups > T2V_MAX_GROUPS || Cin < 32 || (Cin % 32) || Cout < 4 || (Cout % 4)) return false;
-    long mt = 0, ot = 0;
+    long ot = 0;
     int max_rows = 1;
     tab.n = ngroups;
     for (int i = 0; i < ngroups; ++i) {
@@ -4865,153 +4897,79 @@ static bool build_pool_fwd(const t2v_conv_group* groups, int ngroups, int Cin, i
         if (g.ntaps != 9 && g.ntaps != 27) return false;
         if (g.dstride == 0 && g.ntaps != 9) return false;
         for (int r = 0; r < g.ntaps / 3; ++r)
-            for (int d = 0; d < 3; ++d) {
-                const int t = r * 3 + d;
-                if (g.dx[t] != d - 1 || g.dz[t] != g.dz[r * 3] || g.dy[t] != g.dy[r * 3] || g.dz[t] < -1 || g.dz[t] > 1 || g.dy[t] < -1 ||
+            for (int dd = 0; dd < 3; ++dd) {
+                const int t = r * 3 + dd;
+                if (g.dx[t] != dd - 1 || g.dz[t] != g.dz[r * 3] || g.dy[t] != g.dy[r * 3] || g.dz[t] < -1 || g.dz[t] > 1 || g.dy[t] < -1 ||
                     g.dy[t] > 1 || g.widx[t] < 0 || g.widx[t] >= T2V_MAX_TAPS)
                     return false;
                 if (g.dstride == 0 && g.dz[t] != 0) return false;
             }
         if (g.ntaps / 3 > max_rows) max_rows = g.ntaps / 3;
         tab.g[i] = g;
-        tab.tile_start[i] = (int32_t)mt;
         tab.out_start[i] = ot;
-        mt += (pool_rows(g) + 63) / 64;
         ot += pool_rows(g) * Cout;
     }
-    for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) { tab.tile_start[i] = (int32_t)mt; tab.out_start[i] = ot; }
-    p.tiles = mt * ((Cout + 63) / 64);
-    p.vecb = (Cout % 4) == 0;
+    for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) tab.out_start[i] = ot;
+    const long mt = retile(tab, groups, ngroups, 64, pool_rows);
+    d.kernel = PoolKernel::Fwd;
+    d.db = tun().pool_fwd_db;
+    d.tiles = mt * ((Cout + 63) / 64);
+    d.vecb = (Cout % 4) == 0;
     const long rounds = (long)max_rows * (Cin / 32);
     long S = 1;
-    if (p.tiles < 384 && rounds > tun().nosplit_chunks) {          // same rule as build_table: fill ~768 workgroup slots
-        S = (768 + p.tiles - 1) / p.tiles;
+    if (d.tiles < 384 && rounds > tun().nosplit_chunks) {          // same rule as build_table: fill ~768 workgroup slots
+        S = (768 + d.tiles - 1) / d.tiles;
         if (S > rounds / 2) S = rounds / 2;
         if (S > 64) S = 64;
         while (S > 1 && (double)S * ot * 4.0 > 256e6) --S;
         if (S < 1) S = 1;
     }
-    p.S = (int)S;
+    d.S = (int)S;
+    d.grid = dim3((unsigned)mt, (unsigned)((Cout + 63) / 64), (unsigned)d.S);
+    d.block = dim3(256);
+    d.ws_floats = d.S > 1 ? (int64_t)d.S * ot : 0;
     return true;
 }
-// the double-buffered forms of the pooled GEMMs (16-channel rounds, one barrier per round; see conv_igemm_strip3_kernel): the forward
-// takes it by default (-8 %), the data gradient does not (+3 % on its 2-8 round loops). Plan queries report K chunk 16, KS 2 for them.
-static bool pool_fwd_db() { static const bool v = env_long("T2V_POOL_FWD_DB", 1) != 0; return v; }
-static bool pool_dgrad_db() { static const bool v = env_long("T2V_POOL_DGRAD_DB", 0) != 0; return v; }
-extern "C" int64_t t2v_pool_conv_fwd_ws_floats(const t2v_conv_group* groups, int ngroups, int Cin, int Cout) {
-    GroupTable tab;
-    PoolPlan p;
-    if (!build_pool_fwd(groups, ngroups, Cin, Cout, false, tab, p)) return T2V_EINVAL;
-    return p.S > 1 ? (int64_t)p.S * tab.out_start[ngroups] : 0;
-}
-extern "C" int t2v_pool_conv_fwd(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, const float* wp, const float* bias,
-                                 float* ws, int flags, void* stream) {
-    GroupTable tab;
-    PoolPlan p;
-    if (!wp || !build_pool_fwd(groups, ngroups, Cin, Cout, true, tab, p)) return T2V_EINVAL;
-    if (flags & ~(T2V_CONV_BIAS | T2V_CONV_ACCUM)) return T2V_EINVAL;
-    if (p.S > 1 && !ws) return T2V_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    double flops = 0;
-    long Mtot = 0;
-    int taps = 0;
-    for (int i = 0; i < ngroups; ++i) {
-        flops += 2.0 * (double)pool_rows(groups[i]) * Cout * Cin * groups[i].ntaps;
-        Mtot += pool_rows(groups[i]);
-        if (groups[i].ntaps > taps) taps = groups[i].ntaps;
-    }
-    {
-        ProfScope prof(0, flops, s, Mtot, Cin, Cout, taps, ngroups, p.S);
-        int32_t plan_[8] = {9, 64, 64, pool_fwd_db() ? 16 : 32, 1, p.vecb ? 1 : 0, pool_fwd_db() ? 2 : 1, p.S};
-        ProfScope::set_plan(plan_, 8);
-        dim3 grid((unsigned)tab.tile_start[tab.n], (unsigned)((Cout + 63) / 64), (unsigned)p.S);
-        if (pool_fwd_db()) T2V_LAUNCH_PROF((conv_pool_fwd_kernel<64, true>), grid, dim3(256), 0, s, tab, wp, bias, ws, Cin, Cout, flags, p.S);
-        else
-        T2V_LAUNCH_PROF(conv_pool_fwd_kernel<64>, grid, dim3(256), 0, s, tab, wp, bias, ws, Cin, Cout, flags, p.S);
-    }
-    int st = launch_status();
-    if (st) return st;
-    if (p.S > 1) {
-        for (int i = 0; i < ngroups; ++i) {                          // the reduce decodes the bias channel from the OUTPUT extents
-            tab.g[i].D = groups[i].dstride ? groups[i].D / 2 : 1;
-            tab.g[i].H = groups[i].H / 2;
-            tab.g[i].W = groups[i].W / 2;
-        }
-        long blocks = (tab.out_start[ngroups] + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        ProfScope prof_r(4, 0.0, s, Mtot, Cin, Cout, taps, ngroups, p.S);
-        T2V_LAUNCH_PROF(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tab, ws, bias, p.S, Cout, flags);
-    }
-    return launch_status();
-}
-
 // data gradient: rows = voxels of the padded grid, one (ct, cy) class pair per workgroup (blockIdx.y & 3)
-static bool build_pool_dgrad(const t2v_conv_group* groups, int ngroups, int K, int C, bool need_ptrs, GroupTable& tab, PoolPlan& p) {
+static bool decide_pool_dgrad(const t2v_conv_group* groups, int ngroups, int K, int C, bool need_ptrs, GroupTable& tab, PoolLaunch& d) {
     if (!groups || ngroups < 1 || ngroups > T2V_MAX_GROUPS || K < 32 || (K % 32) || C < 4 || (C % 4)) return false;
-    long mt = 0;
     tab.n = ngroups;
     for (int i = 0; i < ngroups; ++i) {
         const t2v_conv_group& g = groups[i];
         if (!pool_member_ok(g, need_ptrs)) return false;
-        if (pool_rows(g) * K >= (1L << 29) || (long)g.N * pool_grid(g) * C * 8 >= (1L << 31)) return false;
+        if (pool_rows(g) * K >= (1L << 29) || pool_grid_rows(g) * C * 8 >= (1L << 31)) return false;
         for (int f = 0; f < 27; ++f) {
             const bool live = g.dstride != 0 || (f / 9) == 1;
             if (live && (g.widx[f] < 0 || g.widx[f] >= T2V_MAX_TAPS)) return false;
         }
         tab.g[i] = g;
-        tab.tile_start[i] = (int32_t)mt;
-        tab.out_start[i] = 0;
-        mt += ((long)g.N * pool_grid(g) + 63) / 64;
     }
-    for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) { tab.tile_start[i] = (int32_t)mt; tab.out_start[i] = 0; }
-    p.tiles = mt * 4 * ((C + 63) / 64);
-    p.vecb = (C % 4) == 0;
+    for (int i = 0; i <= T2V_MAX_GROUPS; ++i) tab.out_start[i] = 0;
+    const long mt = retile(tab, groups, ngroups, 64, pool_grid_rows);
+    d.kernel = PoolKernel::Dgrad;
+    d.db = tun().pool_dgrad_db;
+    d.tiles = mt * 4 * ((C + 63) / 64);
+    d.vecb = (C % 4) == 0;
     // k-split over the channel blocks when the launch cannot fill the chip: every split writes its own set of 8 planes
     long S = 1;
     const long ncb = K / 32;
     // (tiles counts all four class pairs although the pairs of an odd time class leave at once on members without a time axis and
     //  the class (1, 1) runs a quarter of the rounds of (0, 0): up to 576 tiles two sets still pay — 400 tiles x 64 rounds, the
     //  full-clip discriminator's 512 -> 256 block, 192 -> us)
-    static const long split_below = env_long("T2V_POOL_DGRAD_SPLIT_BELOW", 576);
-    if (p.tiles < split_below && ncb >= 4) {
-        S = (768 + p.tiles - 1) / p.tiles;
+    if (d.tiles < tun().pool_dgrad_split_below && ncb >= 4) {
+        S = (768 + d.tiles - 1) / d.tiles;
         if (S > ncb / 2) S = ncb / 2;
         if (S > 8) S = 8;
         if (S < 1) S = 1;
     }
-    p.S = (int)S;
+    d.S = (int)S;
+    d.grid = dim3((unsigned)mt, (unsigned)(4 * ((C + 63) / 64)), (unsigned)d.S);
+    d.block = dim3(256);
+    d.ws_floats = 0;
     return true;
 }
-// number of plane SETS t2v_pool_conv_dgrad writes for these members (its k-split count): the caller allocates
-// [S][8][N, C, Dq, Hq, Wq] per member and hands S to t2v_pool_unbox (job.relu), which sums the sets
-extern "C" int t2v_pool_conv_dgrad_splits(const t2v_conv_group* groups, int ngroups, int K, int C) {
-    GroupTable tab;
-    PoolPlan p;
-    if (!build_pool_dgrad(groups, ngroups, K, C, false, tab, p)) return T2V_EINVAL;
-    return p.S;
-}
-extern "C" int t2v_pool_conv_dgrad(const t2v_conv_group* groups, int ngroups, int K, int C, const float* wp, void* stream) {
-    GroupTable tab;
-    PoolPlan p;
-    if (!wp || !build_pool_dgrad(groups, ngroups, K, C, true, tab, p)) return T2V_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    double flops = 0;
-    long Mtot = 0;
-    for (int i = 0; i < ngroups; ++i) {
-        flops += 2.0 * (double)pool_rows(groups[i]) * K * C * (groups[i].dstride ? 27 : 9);
-        Mtot += (long)groups[i].N * pool_grid(groups[i]);
-    }
-    ProfScope prof(0, flops, s, Mtot, K, C, 27, ngroups, p.S);
-    int32_t plan_[8] = {10, 64, 64, pool_dgrad_db() ? 16 : 32, 1, p.vecb ? 1 : 0, pool_dgrad_db() ? 2 : 1, p.S};
-    ProfScope::set_plan(plan_, 8);
-    dim3 grid((unsigned)tab.tile_start[tab.n], (unsigned)(4 * ((C + 63) / 64)), (unsigned)p.S);
-    if (pool_dgrad_db()) T2V_LAUNCH_PROF(conv_pool_dgrad_kernel<true>, grid, dim3(256), 0, s, tab, wp, K, C);
-    else T2V_LAUNCH_PROF(conv_pool_dgrad_kernel<false>, grid, dim3(256), 0, s, tab, wp, K, C);
-    return launch_status();
-}
-
-// weight gradient: chunks of 32 pooled voxels, one kernel row (dz, dy) per workgroup, k-split like build_wtable
-static bool build_pool_wtable(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, bool need_ptrs, WGroupTable& tab, WgradPlan& p) {
+// weight gradient: chunks of 32 pooled voxels, one kernel row (dz, dy) per workgroup, k-split like decide_wgrad
+static bool decide_pool_wgrad(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, bool need_ptrs, WGroupTable& tab, WgradLaunch& d) {
     if (!groups || ngroups < 1 || ngroups > T2V_MAX_GROUPS || Cin < 1 || Cout < 1 || (kD != 1 && kD != 3)) return false;
     long nch = 0;
     bool any_t = false;
@@ -5027,43 +4985,118 @@ static bool build_pool_wtable(const t2v_conv_group* groups, int ngroups, int Cin
         nch += (pool_rows(g) + WG_BK - 1) / WG_BK;
     }
     for (int i = ngroups; i <= T2V_MAX_GROUPS; ++i) tab.chunk_start[i] = (int32_t)nch;
-    p.nchunks = nch;
-    p.rows3 = true;
-    p.strided = false;
-    p.liverows = any_t ? 0x1ffu : 0x038u;            // kernel rows (dz, dy): all nine, or the dz = 0 ones
-    p.nrows = any_t ? 9 : 3;
-    p.live = any_t ? 0x7ffffffu : (0x1ffu << 9);
-    p.nlive = p.nrows * 3;
-    const long base = (long)((Cout + 63) / 64) * ((Cin + 63) / 64) * p.nrows;
-    const long wg_env = tun().wgrad_target, s_cap = tun().wgrad_scap;
-    const long wg_target = wg_env ? wg_env : 1024;
-    long S = base >= 1024 ? 1 : (wg_target + base - 1) / base;
-    // at least 4 chunks (128 pooled voxels) per split, as for the un-pooled kernels (8 -> 4: -0.04 ms per iteration once the kernel
-    // ran four workgroups per CU; no better before)
-    static const long pool_mincps = env_long("T2V_POOL_WGRAD_MINCPS", 4);
-    long maxS = (nch + pool_mincps - 1) / pool_mincps;
-    if (S > maxS) S = maxS;
-    if (S < 1) S = 1;
-    if (S > s_cap) S = s_cap;
-    const long rounds = (base * S) / 1024, tail = (base * S) % 1024;
-    if (tun().wgrad_quantise && rounds >= 1 && tail > 0 && tail * 5 <= 1024 && (rounds * 1024) / base >= 1) S = (rounds * 1024) / base;
-    p.cps = (int)((nch + S - 1) / S);
-    p.S = (int)((nch + p.cps - 1) / p.cps);
+    d.kernel = WgradKernel::PoolRows3;
+    d.bf16 = d.strided = false;
+    d.nchunks = nch;
+    d.liverows = any_t ? 0x1ffu : 0x038u;            // kernel rows (dz, dy): all nine, or the dz = 0 ones
+    d.nrows = any_t ? 9 : 3;
+    d.live = any_t ? 0x7ffffffu : (0x1ffu << 9);
+    d.nlive = d.nrows * 3;
+    d.grid = dim3((unsigned)(((Cout + 63) / 64) * ((Cin + 63) / 64)), (unsigned)d.nrows);
+    wgrad_set_splits(d, wgrad_ksplit((long)d.grid.x * d.grid.y, nch, tun().pool_wgrad_min_cps), 1, Cin, Cout);
     return true;
+}
+
+static void pool_plan_out(const PoolLaunch& d, int32_t* out) {
+    const int32_t v[8] = {(int32_t)d.kernel, 64, 64, d.db ? 16 : 32, 1, d.vecb ? 1 : 0, d.db ? 2 : 1, d.S};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+}
+// what: 0 forward, 1 data gradient (Cin = K of dL/dy, Cout = channels of the planes), 2 weight gradient of a [.,.,3,3,3] weight
+// (out[] as t2v_conv_fwd_plan / t2v_conv_wgrad_plan)
+extern "C" int t2v_pool_conv_plan(int what, const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int32_t* out) {
+    if (!out) return T2V_EINVAL;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (what == 0 || what == 1) {
+        GroupTable tab;
+        PoolLaunch d;
+        if (!(what == 0 ? decide_pool_fwd(groups, ngroups, Cin, Cout, false, tab, d) : decide_pool_dgrad(groups, ngroups, Cin, Cout, false, tab, d)))
+            return T2V_EINVAL;
+        pool_plan_out(d, out);
+        return T2V_OK;
+    }
+    if (what == 2) {
+        WGroupTable tab;
+        WgradLaunch d;
+        if (!decide_pool_wgrad(groups, ngroups, Cin, Cout, 3, false, tab, d)) return T2V_EINVAL;
+        wgrad_plan_out(d, out, 8);
+        return T2V_OK;
+    }
+    return T2V_EINVAL;
+}
+extern "C" int64_t t2v_pool_conv_fwd_ws_floats(const t2v_conv_group* groups, int ngroups, int Cin, int Cout) {
+    GroupTable tab;
+    PoolLaunch d;
+    if (!decide_pool_fwd(groups, ngroups, Cin, Cout, false, tab, d)) return T2V_EINVAL;
+    return d.ws_floats;
+}
+// number of plane SETS t2v_pool_conv_dgrad writes for these members (its k-split count): the caller allocates
+// [S][8][N, C, Dq, Hq, Wq] per member and hands S to t2v_pool_unbox (job.relu), which sums the sets
+extern "C" int t2v_pool_conv_dgrad_splits(const t2v_conv_group* groups, int ngroups, int K, int C) {
+    GroupTable tab;
+    PoolLaunch d;
+    if (!decide_pool_dgrad(groups, ngroups, K, C, false, tab, d)) return T2V_EINVAL;
+    return d.S;
 }
 extern "C" int64_t t2v_pool_conv_wgrad_slab_floats(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, int want_bias) {
     WGroupTable tab;
-    WgradPlan p;
-    if (!build_pool_wtable(groups, ngroups, Cin, Cout, kD, false, tab, p)) return T2V_EINVAL;
-    return (int64_t)p.S * p.nlive * Cout * Cin + (want_bias ? (int64_t)p.S * Cout : 0);
+    WgradLaunch d;
+    if (!decide_pool_wgrad(groups, ngroups, Cin, Cout, kD, false, tab, d)) return T2V_EINVAL;
+    return d.slab_floats + (want_bias ? d.bias_floats : 0);
+}
+
+extern "C" int t2v_pool_conv_fwd(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, const float* wp, const float* bias,
+                                 float* ws, int flags, void* stream) {
+    GroupTable tab;
+    PoolLaunch d;
+    if (!wp || !decide_pool_fwd(groups, ngroups, Cin, Cout, true, tab, d)) return T2V_EINVAL;
+    if (flags & ~(T2V_CONV_BIAS | T2V_CONV_ACCUM)) return T2V_EINVAL;
+    if (d.S > 1 && !ws) return T2V_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const FwdStats st = fwd_stats(groups, ngroups, Cin, Cout, pool_rows);
+    {
+        ProfScope prof(0, st.flops, s, st.rows, Cin, Cout, st.taps, ngroups, d.S);
+        int32_t plan_[8];
+        pool_plan_out(d, plan_);
+        ProfScope::set_plan(plan_, 8);
+        if (d.db) T2V_LAUNCH_PROF((conv_pool_fwd_kernel<64, true>), d.grid, d.block, 0, s, tab, wp, bias, ws, Cin, Cout, flags, d.S);
+        else T2V_LAUNCH_PROF(conv_pool_fwd_kernel<64>, d.grid, d.block, 0, s, tab, wp, bias, ws, Cin, Cout, flags, d.S);
+    }
+    int st_ = launch_status();
+    if (st_ || d.S == 1) return st_;
+    for (int i = 0; i < ngroups; ++i) {                          // the reduce decodes the bias channel from the OUTPUT extents
+        tab.g[i].D = groups[i].dstride ? groups[i].D / 2 : 1;
+        tab.g[i].H = groups[i].H / 2;
+        tab.g[i].W = groups[i].W / 2;
+    }
+    launch_splitk_reduce(tab, ws, bias, d.S, Cin, Cout, flags, st, s);
+    return launch_status();
+}
+extern "C" int t2v_pool_conv_dgrad(const t2v_conv_group* groups, int ngroups, int K, int C, const float* wp, void* stream) {
+    GroupTable tab;
+    PoolLaunch d;
+    if (!wp || !decide_pool_dgrad(groups, ngroups, K, C, true, tab, d)) return T2V_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    double flops = 0;
+    long Mtot = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        flops += 2.0 * (double)pool_rows(groups[i]) * K * C * (groups[i].dstride ? 27 : 9);
+        Mtot += pool_grid_rows(groups[i]);
+    }
+    ProfScope prof(0, flops, s, Mtot, K, C, 27, ngroups, d.S);
+    int32_t plan_[8];
+    pool_plan_out(d, plan_);
+    ProfScope::set_plan(plan_, 8);
+    if (d.db) T2V_LAUNCH_PROF(conv_pool_dgrad_kernel<true>, d.grid, d.block, 0, s, tab, wp, K, C);
+    else T2V_LAUNCH_PROF(conv_pool_dgrad_kernel<false>, d.grid, d.block, 0, s, tab, wp, K, C);
+    return launch_status();
 }
 static int pool_wgrad_impl(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, float* dw, float* dbias, bool want_bias,
                            float* slab, int flags, void* stream, t2v_wgrad_src* out_src) {
     WGroupTable tab;
-    WgradPlan p;
-    if ((!dw && !out_src) || !slab || !build_pool_wtable(groups, ngroups, Cin, Cout, kD, true, tab, p)) return T2V_EINVAL;
+    WgradLaunch d;
+    if ((!dw && !out_src) || !slab || !decide_pool_wgrad(groups, ngroups, Cin, Cout, kD, true, tab, d)) return T2V_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* bias_part = slab + (size_t)p.S * p.nlive * Cout * Cin;
+    float* bias_part = want_bias ? slab + d.slab_floats : (float*)nullptr;
     const int T = kD * 9;
     TapMap map;
     for (int t = 0; t < T2V_MAX_TAPS; ++t) map.j[t] = -1;
@@ -5071,7 +5104,7 @@ static int pool_wgrad_impl(const t2v_conv_group* groups, int ngroups, int Cin, i
     lrows.n = 0;
     for (int r = 0; r < 9; ++r) lrows.r[r] = 0;
     for (int r = 0; r < 9; ++r)                              // kernel rows (dz, dy) in the 3x3x3 numbering the kernel decodes
-        if ((p.liverows >> r) & 1u) {
+        if ((d.liverows >> r) & 1u) {
             const int rw = kD == 3 ? r : r - 3;              // ... and in the weight's own (a [.,.,3,3] weight only has the dz = 0 rows)
             for (int c = 0; c < 3; ++c) map.j[rw * 3 + c] = lrows.n * 3 + c;
             lrows.r[lrows.n++] = (int8_t)r;
@@ -5079,36 +5112,15 @@ static int pool_wgrad_impl(const t2v_conv_group* groups, int ngroups, int Cin, i
     double flops = 0;
     for (int i = 0; i < ngroups; ++i) flops += 2.0 * (double)pool_rows(groups[i]) * Cout * Cin * (groups[i].dstride ? 27 : 9);
     {
-        ProfScope prof(1, flops, s, p.nchunks * WG_BK, Cin, Cout, p.nlive, ngroups, p.S);
-        int32_t plan_[8] = {11, p.S, p.cps, p.nlive, ((long)Cout * Cin <= 16384 && p.S >= 16) ? 1 : 0,
-                            (int32_t)((long)((Cout + 63) / 64) * ((Cin + 63) / 64) * p.nrows * p.S), 0, 0};
+        ProfScope prof(1, flops, s, d.nchunks * WG_BK, Cin, Cout, d.nlive, ngroups, d.S);
+        int32_t plan_[8];
+        wgrad_plan_out(d, plan_, 8);
         ProfScope::set_plan(plan_, 8);
-        dim3 grid((unsigned)(((Cout + 63) / 64) * ((Cin + 63) / 64)), (unsigned)lrows.n, (unsigned)p.S);
-        T2V_LAUNCH_PROF(conv_pool_wgrad_kernel, grid, dim3(256), 0, s, tab, slab, Cin, Cout, p.cps, lrows, want_bias ? bias_part : (float*)nullptr);
+        T2V_LAUNCH_PROF(conv_pool_wgrad_kernel, d.grid, d.block, 0, s, tab, slab, Cin, Cout, d.cps, lrows, bias_part);
     }
     int st = launch_status();
     if (st) return st;
-    if (out_src) {
-        out_src->slab = slab;
-        out_src->bias_slab = want_bias ? bias_part : (const float*)nullptr;
-        out_src->ntaps = p.nlive;
-        out_src->S = p.S;
-        out_src->tap_stride = (int64_t)Cout * Cin;
-        out_src->split_stride = (int64_t)p.nlive * Cout * Cin;
-        for (int t = 0; t < T2V_MAX_TAPS; ++t) out_src->map[t] = (int8_t)(t < T ? map.j[t] : -1);
-        return T2V_OK;
-    }
-    const float* bias_in = want_bias ? bias_part : (const float*)nullptr;
-    const int accum_bias = (flags & T2V_CONV_ACCUM_BIAS) ? 1 : 0;
-    const long CoCi = (long)Cout * Cin;
-    ProfScope prof2(2, 0.0, s, CoCi, Cin, Cout, T, p.nlive, p.S);
-    if (CoCi <= 16384 && p.S >= 16)
-        T2V_LAUNCH_PROF(wgrad_reduce_small_kernel, dim3((unsigned)((CoCi + 63) / 64), (unsigned)T), dim3(256), 0, s, slab, dw, CoCi, T,
-                   p.nlive, p.S, map, (flags & T2V_CONV_ACCUM) ? 1 : 0, bias_in, dbias, Cout, accum_bias);
-    else
-        T2V_LAUNCH_PROF(wgrad_reduce_kernel, dim3((unsigned)((CoCi + 63) / 64)), dim3(256), 0, s, slab, dw, CoCi, T, p.nlive, p.S, map,
-                   (flags & T2V_CONV_ACCUM) ? 1 : 0, bias_in, dbias, Cout, accum_bias);
-    return launch_status();
+    return wgrad_finish(d, T, map, slab, bias_part, dw, dbias, Cin, Cout, flags, s, out_src);
 }
 extern "C" int t2v_pool_conv_wgrad(const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int kD, float* dw, float* dbias,
                                    float* slab, int flags, void* stream) {
@@ -5119,29 +5131,6 @@ extern "C" int t2v_pool_conv_wgrad_partial(const t2v_conv_group* groups, int ngr
                                            int want_bias, int flags, t2v_wgrad_src* out_src, void* stream) {
     if (!out_src) return T2V_EINVAL;
     return pool_wgrad_impl(groups, ngroups, Cin, Cout, kD, nullptr, nullptr, want_bias != 0, slab, flags, stream, out_src);
-}
-// what: 0 forward, 1 data gradient (Cin = K of dL/dy, Cout = channels of the planes), 2 weight gradient
-extern "C" int t2v_pool_conv_plan(int what, const t2v_conv_group* groups, int ngroups, int Cin, int Cout, int32_t* out) {
-    if (!out) return T2V_EINVAL;
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    if (what == 0 || what == 1) {
-        GroupTable tab;
-        PoolPlan p;
-        if (!(what == 0 ? build_pool_fwd(groups, ngroups, Cin, Cout, false, tab, p) : build_pool_dgrad(groups, ngroups, Cin, Cout, false, tab, p)))
-            return T2V_EINVAL;
-        const bool db = what == 0 ? pool_fwd_db() : pool_dgrad_db();
-        out[0] = what == 0 ? 9 : 10; out[1] = 64; out[2] = 64; out[3] = db ? 16 : 32; out[4] = 1; out[5] = p.vecb ? 1 : 0; out[6] = db ? 2 : 1; out[7] = p.S;
-        return T2V_OK;
-    }
-    if (what == 2) {
-        WGroupTable tab;
-        WgradPlan p;
-        if (!build_pool_wtable(groups, ngroups, Cin, Cout, 3, false, tab, p)) return T2V_EINVAL;
-        out[0] = 11; out[1] = p.S; out[2] = p.cps; out[3] = p.nlive; out[4] = ((long)Cout * Cin <= 16384 && p.S >= 16) ? 1 : 0;
-        out[5] = (int32_t)((long)((Cout + 63) / 64) * ((Cin + 63) / 64) * p.nrows * p.S);
-        return T2V_OK;
-    }
-    return T2V_EINVAL;
 }
 
 extern "C" int t2v_wgrad_dest_bytes(void) { return (int)sizeof(t2v_wgrad_dest); }
