@@ -259,6 +259,10 @@ int t2v_upsample2x_add(const float* x, const float* h, float* y, int64_t planes,
  * running stats updated with `momentum` (unbiased variance), y = relu?((x-mean)*invstd*gamma+beta).
  * stats[0:C] = mean, stats[C:2C] = invstd (saved for backward). */
 int64_t t2v_bn_ws_floats(int N, int C, int64_t S);   /* floats of `ws` for bn_stats / bn_bwd */
+/* Launch plan of every entry point below (host arithmetic, no launch): out[0] = slices per channel of the statistics
+ * passes (1..64), out[1] = workgroups per channel of the fused merge + apply passes. Used by the tests to assert which
+ * cut a case gets. */
+int t2v_bn_plan(int N, int C, int64_t S, int32_t* out /* [2] */);
 int t2v_bn_stats(const float* x, float* stats, float* running_mean, float* running_var, float* ws, int N, int C,
                  int64_t S, float momentum, float eps, void* stream);
 int t2v_bn_apply(const float* x, const float* stats, const float* gamma, const float* beta, float* y,

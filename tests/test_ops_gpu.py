@@ -522,30 +522,42 @@ def test_scale_add_rowsum_double_backward():
         close(td.grad, tr.grad, rtol=1e-3, atol=1e-3)
 
 
-def test_batchnorm_tanh_upsample():
+def test_tanh_upsample():
+    """(The BatchNorm in front of these two lives in tests/test_norm_gpu.py.)"""
     from txt2vid_amd import functional as TF
     x = rnd(1, 4, 6, 5, 5)
-    gamma, beta = 1 + 0.1 * rnd(2, 6), 0.1 * rnd(3, 6)
-    rm, rv = 0.1 * rnd(4, 6), 1 + 0.1 * torch.rand(6)
-    xr, gr, br = x.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
-    rmr, rvr = rm.clone(), rv.clone()
-    yr = torch.tanh(F.interpolate(F.relu(F.batch_norm(xr, rmr, rvr, gr, br, True, 0.1, 1e-5)), scale_factor=2))
+    xr = x.clone().requires_grad_(True)
+    yr = torch.tanh(F.interpolate(F.relu(xr), scale_factor=2))
     gy = rnd(5, *yr.shape)
     (yr * gy).sum().backward()
     xd = x.to(dev()).requires_grad_(True)
-    gd, bd = torch.nn.Parameter(gamma.to(dev())), torch.nn.Parameter(beta.to(dev()))
-    rmd, rvd = rm.to(dev()), rv.to(dev())
-    yd = TF.tanh(TF.upsample2x(TF.batch_norm_act(xd, gd, bd, rmd, rvd, True, 0.1, 1e-5, True)))
+    yd = TF.tanh(TF.upsample2x(TF.relu(xd)))
     close(yd, yr)
     (yd * gy.to(dev())).sum().backward()
     close(xd.grad, xr.grad, rtol=1e-3, atol=1e-4)
-    close(gd.grad, gr.grad, rtol=1e-3, atol=1e-4)
-    close(bd.grad, br.grad, rtol=1e-3, atol=1e-4)
-    close(rmd, rmr)
-    close(rvd, rvr)
-    # eval mode
-    ye = TF.batch_norm_act(x.to(dev()), gd, bd, rmd, rvd, False, 0.1, 1e-5, False)
-    close(ye, F.batch_norm(x, rmr, rvr, gamma, beta, False, 0.1, 1e-5))
+
+
+@pytest.mark.parametrize('shape', [(2, 3, 1, 7), (3, 5, 1, 1), (4, 6, 5, 5)])
+def test_upsample2x_and_upsample_add_at_odd_shapes(shape):
+    """Nearest x2 up-sampling is a copy and `upsample_add` one add per element: the forward passes are exact."""
+    from txt2vid_amd import functional as TF
+    x = rnd(21, *shape)
+    h = rnd(22, shape[0], shape[1], 2 * shape[2], 2 * shape[3])
+    gy = rnd(23, *h.shape)
+    xr, hr = x.clone().requires_grad_(True), h.clone().requires_grad_(True)
+    ur = F.interpolate(xr, scale_factor=2)
+    gur, = torch.autograd.grad((ur * gy).sum(), [xr], retain_graph=True)
+    gxr, ghr = torch.autograd.grad(((ur + hr) * gy).sum(), [xr, hr])
+    xd, hd = x.to(dev()).requires_grad_(True), h.to(dev()).requires_grad_(True)
+    ud = TF.upsample2x(xd)
+    assert torch.equal(ud.detach().cpu(), ur.detach())
+    gud, = torch.autograd.grad((ud * gy.to(dev())).sum(), [xd])
+    close(gud, gur, rtol=1e-5, atol=1e-5)                    # a sum of four terms in another order: a few roundings of 2^-24 of sum |terms|
+    sd = TF.upsample_add(xd, hd)
+    assert torch.equal(sd.detach().cpu(), (ur + hr).detach())
+    gxd, ghd = torch.autograd.grad((sd * gy.to(dev())).sum(), [xd, hd])
+    close(gxd, gxr, rtol=1e-5, atol=1e-5)
+    assert torch.equal(ghd.cpu(), ghr)
 
 
 @pytest.mark.parametrize('members,cin,cout', [

@@ -678,6 +678,14 @@ extern "C" int64_t t2v_bn_ws_floats(int N, int C, int64_t S) {
     if (N < 1 || C < 1 || S < 1) return T2V_EINVAL;
     return (int64_t)C * bn_split(N, C, (long)S) * 3 + 2 * C;
 }
+// how the launchers below cut [N,C,S] (host arithmetic, no launch): out[0] = slices per channel of the statistics passes,
+// out[1] = workgroups per channel of the fused second passes
+extern "C" int t2v_bn_plan(int N, int C, int64_t S, int32_t* out) {
+    if (!out || N < 1 || C < 1 || S < 1) return T2V_EINVAL;
+    out[0] = bn_split(N, C, (long)S);
+    out[1] = bn_slices(N, C, (long)S);
+    return T2V_OK;
+}
 extern "C" int t2v_bn_stats(const float* x, float* stats, float* rm, float* rv, float* ws, int N, int C, int64_t S, float momentum,
                             float eps, void* st) {
     if (!x || !stats || !ws || N < 1 || C < 1 || S < 1) return T2V_EINVAL;
