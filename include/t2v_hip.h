@@ -463,6 +463,28 @@ int t2v_ema_tick(float* count, void* stream);
 /* Exchanges the contents of e and p of every job in place (the addresses stay the same). */
 int t2v_swap_multi(const t2v_ema_job* jobs, int njobs, void* stream);
 
+/* ---- spectral normalisation of the discriminator's weights (Miyato et al. 2018; --D_sn, not in the reference) ------------ */
+/* Grouped like t2v_adam_multi: `jobs` is a HOST array, at most T2V_SN_MAX_JOBS per call, device pointers inside. A job is one
+   weight seen as a row-major matrix W [M = Cout, K = Cin*kD*kH*kW] (Linear: [out, in]); all tensors contiguous fp32:
+     w      the master W                       what   W / sigma: the storage every kernel of the discriminator multiplies with
+     u [M], v [K], sigma [1]                   g      dL/dWhat on entry of t2v_sn_project (unused by t2v_sn_refresh, may be NULL)
+   t2v_sn_refresh runs n_iter >= 1 power iterations and then scales:
+     t = W^T u ; v = t / max(|t|, eps) ; s = W v ; u = s / max(|s|, eps) ; sigma = u . s ;   what = W / sigma
+   from_param != 0: W is read from `what` (the optimiser has just updated it there) and saved to `w` by the scaling pass.
+   sigma == 0 (W v = 0, e.g. a zero matrix; u and v are then 0, never NaN) divides by 1: what = W.
+   t2v_sn_project maps the gradient with respect to What to the one with respect to W, u and v held constant:
+     c = <g, what> ;  g = (g - c u v^T) / sigma        (sigma == 0 divides by 1);   restore != 0: what = w afterwards.
+   `ws`: at least t2v_sn_ws_floats(jobs, njobs) floats, 16-byte aligned, owned by the caller (no allocation inside; sums that span
+   workgroups go through it and are added in a fixed order: no atomics, the same bits on every run). Launches: 5 * n_iter + 1
+   per t2v_sn_refresh, 3 per t2v_sn_project, whatever njobs is. Capturable. T2V_EINVAL on NULL pointers, M < 1, K < 1,
+   M * K > INT_MAX, njobs outside 1..T2V_SN_MAX_JOBS, n_iter < 1, eps <= 0 or a workspace that is too small. */
+#define T2V_SN_MAX_JOBS 32
+typedef struct t2v_sn_job { float* w; float* what; float* u; float* v; float* sigma; float* g; int32_t M, K; } t2v_sn_job;
+int64_t t2v_sn_ws_floats(const t2v_sn_job* jobs, int njobs);
+int t2v_sn_refresh(const t2v_sn_job* jobs, int njobs, float* ws, int64_t ws_floats, int n_iter, float eps, int from_param,
+                   void* stream);
+int t2v_sn_project(const t2v_sn_job* jobs, int njobs, float* ws, int64_t ws_floats, int restore, void* stream);
+
 /* ---- pyramid (trainer.py:131-165, layers.py:106-111) ------------------------------------------- */
 /* y[b,c,t,h,w] = x[b*sb, c, t*st+bt, (h*H)/Ho, (w*W)/Wo]  — Subsample + nearest F.interpolate. */
 int t2v_pyramid_gather(const float* x, float* y, int B, int C, int T, int H, int W, int Bo, int To, int Ho, int Wo,

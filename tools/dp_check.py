@@ -3,11 +3,12 @@ the graph-replayed iteration with the gradient sink + the per-step arena all-red
 same weights, and those must differ from what a rank would have learnt alone (the exchange is live).
 
     T2V_DIST_BACKEND=gloo T2V_SINGLE_DEVICE=1 python -m torch.distributed.run --nproc-per-node 2 \\
-        --master-addr 127.0.0.1 --master-port 29531 tools/dp_check.py [--discrim_steps N] [--gen_steps M] [--cond [--ca_dim D]]
+        --master-addr 127.0.0.1 --master-port 29531 tools/dp_check.py [--discrim_steps N] [--gen_steps M] [--cond [--ca_dim D]] [--D_sn]
 
 With a schedule other than 1:1 the line also reports the graphs and the exchanges ('D' / 'G') of one replayed iteration.
 --cond: the text-conditioned models (a randomly initialised Bi-LSTM sentence encoder, 8-token captions per rank); --ca_dim D > 0
 puts the generator's conditioning augmentation in front of its fc (built here: bench.build_models has no such argument).
+--D_sn: spectral normalisation of the discriminator; its master weights, u, v and sigma join the compared state.
 """
 import argparse
 import os
@@ -33,6 +34,7 @@ ap.add_argument('--discrim_steps', type=int, default=1)
 ap.add_argument('--gen_steps', type=int, default=1)
 ap.add_argument('--cond', action='store_true')
 ap.add_argument('--ca_dim', type=int, default=0)
+ap.add_argument('--D_sn', action='store_true')
 args = ap.parse_args()
 if args.ca_dim and not args.cond:
     ap.error('--ca_dim needs --cond')
@@ -76,6 +78,9 @@ def run(sync):
     else:
         gen, dis, optD, optG, losses, CondGan = bench.build_models(dev)         # same seed -> identical replicas
     gan = CondGan(gen=gen, discrims=[dis], cond_encoder=txt, discrim_names=['video'], gp_scale=float(world if sync else 1))
+    if args.D_sn:
+        from txt2vid_amd.gan.spectral import SpectralNorm, attach
+        attach(gan, optD, SpectralNorm([dis], seed=100))                        # same seed on every rank, like the weights
     gs = None
     if sync:
         arenas = {'D': tdist.model_arena(dis, TF.copy_into), 'G': tdist.model_arena(gen, TF.copy_into)}
@@ -105,7 +110,11 @@ def run(sync):
         del seen[:]
         lD, lG = step.step(pool[i % 2], codes)
     torch.cuda.synchronize()
-    chk = torch.stack([p.detach().double().sum() for p in list(dis.parameters()) + list(gen.parameters())])
+    state = list(dis.parameters()) + list(gen.parameters())
+    if args.D_sn:
+        sn = gan.discrim_sn
+        state += sn.orig + sn.u + sn.v + sn.sigma
+    chk = torch.stack([p.detach().double().sum() for p in state] + [p.detach().double().abs().sum() for p in state])
     return chk, float(lD), float(lG), (step.n_graphs, ''.join(seen))
 
 
@@ -122,6 +131,8 @@ if rank == 0:
                                                                                          n_graphs, exchanges)
     if args.cond:
         sched += '; text-conditioned, ca_dim %d' % args.ca_dim
+    if args.D_sn:
+        sched += '; spectral norm (W, u, v, sigma compared too)'
     print('DP_CHECK replicas identical after 5 iterations: %s; differs from a solo run by %.3e; lossD %.5f lossG %.5f%s' %
           (same, moved, lD, lG, sched))
     assert same and moved > 1e-6

@@ -38,6 +38,15 @@ class EmaJob(C.Structure):
     _fields_ = [('e', C.c_void_p), ('p', C.c_void_p), ('n', C.c_int64)]
 
 
+class SnJob(C.Structure):
+    """t2v_sn_job (include/t2v_hip.h)."""
+    _fields_ = [('w', C.c_void_p), ('what', C.c_void_p), ('u', C.c_void_p), ('v', C.c_void_p), ('sigma', C.c_void_p), ('g', C.c_void_p),
+                ('M', C.c_int32), ('K', C.c_int32)]
+
+
+SN_MAX_JOBS = 32
+
+
 class PoolJob(C.Structure):
     """t2v_pool_job (include/t2v_hip.h)."""
     _fields_ = [('x', C.c_void_p), ('x2', C.c_void_p), ('y', C.c_void_p), ('add', C.c_void_p), ('NC', C.c_int32), ('D', C.c_int32), ('H', C.c_int32),
@@ -202,6 +211,9 @@ SIGNATURES = {
     't2v_ema_multi': [_P, _I, _F, _F, _P, _F, _P],
     't2v_ema_tick': [_P, _P],
     't2v_swap_multi': [_P, _I, _P],
+    't2v_sn_ws_floats': [_P, _I],
+    't2v_sn_refresh': [_P, _I, _P, _L, _I, _F, _I, _P],
+    't2v_sn_project': [_P, _I, _P, _L, _I, _P],
     't2v_pyramid_gather': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     't2v_copy2d': [_P, _L, _P, _L, _L, _L, _P],
     't2v_cast_bf16': [_P, _P, _L, _I, _P],
@@ -235,7 +247,7 @@ SIGNATURES = {
     't2v_prof_end': [C.POINTER(C.c_double), _I],
     't2v_version': [],
 }
-_RESTYPE = {'t2v_multi_ws_floats': C.c_int64, 't2v_pool_conv_fwd_ws_floats': C.c_int64, 't2v_pool_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_grouped_bias_slab_floats': C.c_int64, 't2v_conv_fwd_grouped_ws_floats': C.c_int64,
+_RESTYPE = {'t2v_multi_ws_floats': C.c_int64, 't2v_sn_ws_floats': C.c_int64, 't2v_pool_conv_fwd_ws_floats': C.c_int64, 't2v_pool_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_grouped_bias_slab_floats': C.c_int64, 't2v_conv_fwd_grouped_ws_floats': C.c_int64,
             't2v_conv_wgrad_grouped_slab_floats': C.c_int64, 't2v_conv_fwd_ws_floats': C.c_int64, 't2v_channel_sum_ws_floats': C.c_int64, 't2v_channel_sum_grouped_ws_floats': C.c_int64, 't2v_bn_ws_floats': C.c_int64, 't2v_version': C.c_char_p}
 
 _lib = None

@@ -37,6 +37,7 @@ class CondGan(object):
         self.discrim_lambdas = discrim_lambdas
         self.gp_scale = gp_scale          # data-parallel: world_size, else 1
         self.gen_ema = gen_ema            # gan.ema.GenAverage of `gen` (--G_ema, not in the reference), or None
+        self.discrim_sn = None            # gan.spectral.SpectralNorm of `discrims` (--D_sn, not in the reference), or None
 
     def _discrim_weighted_sum(self, losses, kl=None, kl_coeff=0.0):
         """cond_gan.py:26-31: mean over discriminators, or lambda-weighted sum. `kl`: the generator's conditioning-augmentation
@@ -268,6 +269,9 @@ class CondGan(object):
             # extra keys next to the reference's layout (its loader reads named keys only): the averaged parameters by name
             res['gen_ema'] = self.gen_ema.state_dict()
             res['gen_ema_updates'] = self.gen_ema.updates
+        if self.discrim_sn is not None:
+            # the discriminators' own `weight` entries hold W / sigma; the master weights and the power-iteration vectors go here
+            res['discrim_sn'] = self.discrim_sn.state_dict()
         return res
 
     def load_from_dict(self, to_load):

@@ -41,7 +41,7 @@ def _aug_policy(text):
 
 def add_params_to_parser(parser):
     """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema,
-    --G_ema_start and --D_aug are new."""
+    --G_ema_start, --D_aug and --D_sn are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
     parser.add_argument('--log_period', type=int, default=20)
@@ -68,6 +68,9 @@ def add_params_to_parser(parser):
     parser.add_argument('--D_aug', type=_aug_policy, default='',
                         help='(new) differentiable augmentation of every clip the discriminator sees: a comma-separated subset of '
                              'color,translation,cutout (applied in that order); empty = off')
+    parser.add_argument('--D_sn', action='store_true', default=False,
+                        help='(new) spectral normalisation of every Conv3d / Linear weight of the discriminators: one power '
+                             'iteration after each discriminator update')
     return parser
 
 

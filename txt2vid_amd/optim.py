@@ -49,6 +49,7 @@ class Adam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = 1.0
         self.step_dev = None          # device-resident step counter (set by `make_capturable`)
+        self.weight_hook = None       # gan.spectral.SpectralNorm of this optimiser's weights (--D_sn), or None
 
     def make_capturable(self, device):
         """Keep the step number on the device so that a captured HIP graph applies the right bias
@@ -85,6 +86,8 @@ class Adam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         TF.grad_sink_flush()                  # (no-op unless a backward pass left k-split partial sums pending)
+        if self.weight_hook is not None:
+            self.weight_hook.project_grads()  # spectral norm: dL/dWhat -> dL/dW, and the master W back into the parameters
         if self.step_dev is not None:
             b1, b2 = self.param_groups[0]['betas']
             TF.check(TF.lib().t2v_adam_tick(TF._p(self.step_dev), b1, b2, TF._stream()), 't2v_adam_tick')
@@ -119,6 +122,10 @@ class Adam(torch.optim.Optimizer):
                 touched.append(p)
             for step, items in by_step.items():
                 TF.adam_step_multi(items, group['lr'], b1, b2, group['eps'], step, self.grad_scale, self.step_dev)
+        if self.weight_hook is not None:
+            # spectral norm: the parameters hold W / sigma again before they are re-packed — EVERY normalised weight does, also one
+            # that had no gradient in this step (u, v and sigma moved on), so all of them join the re-pack
+            touched = self.weight_hook.refresh(touched)
         TF.bump_weight_epoch(touched)   # their packed weights are stale ...
         TF.repack_params(touched)       # ... refresh them in place right away (same addresses for graph replay)
         return None
@@ -133,6 +140,7 @@ class SGD(torch.optim.Optimizer):
             raise NotImplementedError('the reference only passes lr and momentum')
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=0, nesterov=False))
         self.grad_scale = 1.0
+        self.weight_hook = None       # as in Adam
 
     def make_capturable(self, device):
         """Nothing step-dependent lives on the host once the momentum buffers exist (they do after the eager warm-up)."""
@@ -145,6 +153,8 @@ class SGD(torch.optim.Optimizer):
     def step(self, closure=None):
         from ._lib import AdamJob
         TF.grad_sink_flush()
+        if self.weight_hook is not None:
+            self.weight_hook.project_grads()
         touched = []
         for group in self.param_groups:
             mu = float(group['momentum'])
@@ -171,6 +181,8 @@ class SGD(torch.optim.Optimizer):
                     a.p, a.g, a.m, a.v, a.n = p.data_ptr(), g.data_ptr(), (m.data_ptr() if m is not None else None), None, p.numel()
                 TF.check(TF.lib().t2v_sgd_multi(arr, len(items), group['lr'], mu, self.grad_scale, is_first, TF._stream()),
                          't2v_sgd_multi')
+        if self.weight_hook is not None:
+            touched = self.weight_hook.refresh(touched)
         TF.bump_weight_epoch(touched)
         TF.repack_params(touched)
         return None

@@ -34,6 +34,8 @@ def _model(spec, args, kind='D', **kw):
 
 
 def main(args):
+    from ..gan.spectral import check_flags, check_checkpoint
+    check_flags(args)
     from .. import dist as tdist
     rank, world = tdist.init_from_env('nccl')
     from ..util.misc import limit_host_threads
@@ -88,11 +90,12 @@ def main(args):
     else:
         optD = Adam(D_params, lr=args.D_lr, betas=(args.D_beta1, args.D_beta2))
         optG = Adam(G_params, lr=args.G_lr, betas=(args.G_beta1, args.G_beta2))
-    resumed_rng, resumed_iter, resumed_ema = None, 0, None
+    resumed_rng, resumed_iter, resumed_ema, resumed_sn = None, 0, None, None
     gan = CondGan(gen=gen, discrims=discrims, cond_encoder=txt_encoder, discrim_names=args.D_names,
                   discrim_lambdas=args.D_lambdas, gp_scale=float(world))
     if args.weights is not None:
         to_load = torch.load(args.weights, map_location=device, weights_only=False)
+        resumed_sn = check_checkpoint(to_load, args.D_sn, args.weights)
         gan.load_from_dict(to_load)
         if 'optD' in to_load:
             optD.load_state_dict(to_load['optD'])
@@ -121,6 +124,16 @@ def main(args):
             gan.gen_ema.load_state_dict(*resumed_ema)
         status('Averaged generator: decay %g after %d updates (%d updates so far)' % (args.G_ema, args.G_ema_start,
                                                                                      gan.gen_ema.updates))
+    if args.D_sn:
+        # spectral normalisation of the discriminators (not in the reference), built from the loaded / initialised and synchronised
+        # weights: a checkpoint with its state continues bit for bit, any other has its weights taken as W. u is drawn from a
+        # generator of its own seeded with the run's seed (the same on every rank), so the replicas stay identical without an
+        # exchange and no draw of the training loop moves
+        from ..gan.spectral import SpectralNorm, attach
+        attach(gan, optD, SpectralNorm(discrims, seed=seed, state=resumed_sn))
+        status('Spectral normalisation of %d discriminator weights (%s)' % (
+            len(gan.discrim_sn.params), 'state from the checkpoint' if resumed_sn is not None else '%d initial power iterations'
+            % gan.discrim_sn.n_init))
     if resumed_rng is not None and rank == 0:
         # checkpoints written by this build carry the writer's (rank 0's) generator states: the resumed run continues the draw
         # sequence where the saved one stopped (reference-written files have no such key and start from --seed)
