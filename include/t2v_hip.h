@@ -212,8 +212,6 @@ int t2v_relu(const float* x, float* y, int64_t n, void* stream);                
 int t2v_relu_mask(const float* g, const float* x, float* gx, int64_t n, void* stream); /* g*(x>0)   */
 int t2v_add(const float* a, const float* b, float* y, int64_t n, void* stream);  /* layers.py:96     */
 int t2v_axpby(float alpha, const float* a, float beta, const float* b, float* y, int64_t n, void* stream);
-int t2v_scale_dev(const float* s, float mul, const float* a, float* y, int64_t n, void* stream); /* y = (*s*mul)*a */
-int t2v_dot(const float* a, const float* b, float* out, float* ws /*256 floats*/, int64_t n, int accum, void* stream);
 int t2v_fill(float* y, float v, int64_t n, void* stream);
 int t2v_tanh(const float* x, float* y, int64_t n, void* stream);                 /* layers.py:258    */
 int t2v_tanh_bwd(const float* g, const float* y, float* gx, int64_t n, void* stream);
@@ -237,12 +235,6 @@ typedef struct t2v_pool_job {
 } t2v_pool_job;
 int t2v_avgpool3d_multi(const t2v_pool_job* jobs, int njobs, void* stream);
 int t2v_avgpool3d_bwd_multi(const t2v_pool_job* jobs, int njobs, void* stream);
-
-/* max_pool [1,2,2] / [2,2] (layers.py:26-27,57-58): y + flat argmax index inside the (H,W) plane.
- * `_scatter`: gx = 0 except gx[idx] = g;  `_gather`: y = x[idx]. */
-int t2v_maxpool2x2(const float* x, float* y, int32_t* idx, int64_t planes, int H, int W, void* stream);
-int t2v_maxpool2x2_scatter(const float* g, const int32_t* idx, float* gx, int64_t planes, int H, int W, void* stream);
-int t2v_maxpool2x2_gather(const float* x, const int32_t* idx, float* y, int64_t planes, int H, int W, void* stream);
 
 /* sum over the S = T*H*W voxels of each (n,c) row (resnet3d.py:48) and its broadcast adjoint. */
 int t2v_rowsum(const float* x, float* y, int64_t rows, int64_t S, void* stream);
@@ -334,10 +326,6 @@ int t2v_lstm_step_bwd_fused(const float* gh, const float* gnext, const float* w1
 /* C[b] = alpha * op(A[b]) x op(B[b]); row-major A[b]: (ta? K x M : M x K), B[b]: (tb? N x K : K x N). */
 int t2v_bmm(const float* A, const float* B, float* C, int batch, int M, int N, int K, int ta, int tb,
             int accum, void* stream);
-int t2v_softmax(const float* x, float* y, int64_t rows, int n, void* stream);            /* layers.py:33 */
-int t2v_softmax_bwd(const float* y, const float* gy, float* gx, int64_t rows, int n, void* stream);
-/* adjoint of softmax_bwd w.r.t. y: gyv = gg*(gy - s) - gy*sum(gg*y), s = sum(gy*y) */
-int t2v_softmax_bwd_bwd_y(const float* y, const float* gy, const float* gg, float* out, int64_t rows, int n, void* stream);
 
 /* ---- sentence encoder (txt2vid/models/txt/basic.py:49-70: packed-sequence nn.LSTM, forward only) -----------------
  * One time step of one (layer, direction): pre = xproj_t[b] (row stride xstride; = x_t W_ih^T + b_ih + b_hh from one GEMM
@@ -384,10 +372,11 @@ int t2v_argmax_rows(const float* x, int32_t* idx, int64_t rows, int V, void* str
  *   T2V_MJ_SCALE            out = scalar[0] * a                         n = elements
  *   T2V_MJ_SCALE_ADD        out = scalar[0] * a + b                     (layers.py:36,68: gamma * o + x)
  *   T2V_MJ_DOT              jobs[0].out[0] (+= if jobs[0].f0) sum over ALL jobs of <a, b>; ws: t2v_multi_ws_floats floats
- *   T2V_MJ_MAXPOOL          out = maxpool2x2(a), out2 = int32 argmax    n = planes, d0 = H, d1 = W  (layers.py:26-27,57-58)
+ *   T2V_MJ_MAXPOOL          out = maxpool2x2(a), out2 = int32 flat argmax inside the (H,W) plane   n = planes, d0 = H, d1 = W  (layers.py:26-27,57-58)
  *   T2V_MJ_MAXSCATTER       out[planes,H,W] = scatter(a = g, b = idx)   T2V_MJ_MAXGATHER: out = a[b = idx]
  *   T2V_MJ_SOFTMAX          out = softmax over rows of a                n = rows, d0 = row length
- *   T2V_MJ_SOFTMAX_BWD      out = a*(b - sum(a*b))  (a = y, b = gy);  _BWD_BWD_Y: a = y, b = gy, c = gg (see t2v_softmax_bwd_bwd_y)
+ *   T2V_MJ_SOFTMAX_BWD      out = a*(b - sum(a*b))  (a = y, b = gy)
+ *   T2V_MJ_SOFTMAX_BWD_BWD_Y  adjoint of _BWD w.r.t. y: out = c*(b - sum(a*b)) - b*sum(c*a)   (a = y, b = gy, c = gg)
  *   T2V_MJ_BMM              out[b] = op(a[b]) @ op(b[b])                n = batch, d0 = M, d1 = N, d2 = K, f0 = ta, f1 = tb
  *   T2V_MJ_RELU_MASK        out = b > 0 ? a : 0                         n = elements (ReLU adjoint over several tensors)
  *   T2V_MJ_ROWSUM           out[row] = sum_s a[row][s]                  n = rows, d0 = S (resnet3d.py:48 over all levels)
@@ -608,7 +597,7 @@ const char* t2v_version(void);
  * phi[:, j]) g[c][j]; theta [b,C8,N], phi [b,C8,Nk], g [b,C2,Nk], o [b,C2,N], lse [b,N] (row log-sum-exp, kept for the
  * adjoint). t2v_nonlocal_bwd: dtheta, dphi, dg from dL/do with beta recomputed from lse; ws: b*N floats.
  * Built for the head sizes of the generator's block (C8 = 4, C2 = 16: t2v_nonlocal_ok); other sizes and the
- * discriminator's 3-D block (which needs a second-order adjoint) stay on t2v_bmm / t2v_softmax. */
+ * discriminator's 3-D block (which needs a second-order adjoint) stay on the T2V_MJ_BMM / T2V_MJ_SOFTMAX jobs of t2v_multi. */
 int t2v_nonlocal_ok(int C8, int C2);
 int t2v_nonlocal_fwd(const float* theta, const float* phi, const float* g, float* o, float* lse, int b, int C8, int C2, int N,
                      int Nk, void* stream);

@@ -26,7 +26,7 @@ def built():
 
 def test_header_declares_the_hot_path():
     syms = declared_symbols()
-    for must in ('t2v_conv_fwd', 't2v_conv_wgrad', 't2v_pack_weight', 't2v_bn_stats', 't2v_softmax', 't2v_bmm',
+    for must in ('t2v_conv_fwd', 't2v_conv_wgrad', 't2v_pack_weight', 't2v_bn_stats', 't2v_multi', 't2v_bmm',
                  't2v_lstm_gates', 't2v_rsgan', 't2v_row_sqnorm', 't2v_adam', 't2v_pyramid_gather'):
         assert must in syms
 

@@ -103,6 +103,109 @@ def test_attention2d(golden):
         close(p.grad, g['at2_g_' + k])
 
 
+# ---- stand-alone blocks run as groups of one: each against the plain fp32 PyTorch restatement (the oracle) on the CPU ----------
+
+def _seeded(module, seed, gamma=None):
+    """(module on the device, its parameters as CPU leaves for the oracle): torch's default initialisation under `seed`."""
+    torch.manual_seed(seed)
+    m = module()
+    if gamma is not None:
+        with torch.no_grad():
+            m.gamma.fill_(gamma)                                  # (initialised to 0: the block would be the identity)
+    P = {k: v.detach().clone().requires_grad_(True) for k, v in m.state_dict().items()}
+    return m.to(DEV), P
+
+
+def _grads_close(m, P, rtol, atol):
+    for k, p in m.named_parameters():
+        assert p.grad is not None, k
+        close(p.grad, P[k].grad, rtol=rtol, atol=atol)
+
+
+def _attention_first_order(cls, ref, shape, x_grad, fused=None):
+    m, P = _seeded(lambda: cls(16), 31, gamma=0.7)                # ch // 8 = 2, ch // 2 = 8: heads narrower than any tile
+    if fused is not None:
+        m.fused_attend = fused
+    x0, gy = rnd(32, *shape), rnd(33, *shape)
+    x, xr = x0.to(DEV).requires_grad_(x_grad), x0.clone().requires_grad_(x_grad)
+    y, yr = m(x), ref(P, '', xr)
+    # bounds of the non-local op tests (test_ops_gpu.test_maxpool_softmax_bmm_double_backward / test_scale_add_rowsum_...)
+    close(y, yr, rtol=1e-4, atol=1e-4)
+    (y * gy.to(DEV)).sum().backward()
+    (yr * gy).sum().backward()
+    if x_grad:
+        close(x.grad, xr.grad, rtol=1e-3, atol=1e-3)
+    _grads_close(m, P, rtol=1e-3, atol=1e-3)
+
+
+def test_attention3d_alone_is_a_group_of_one():
+    """`Attention3d(16)(x)` = `nonlocal_levels(att, [x])[0]`: output, dL/dx and the five parameter gradients."""
+    from txt2vid_amd.models.layers import Attention3d
+    _attention_first_order(Attention3d, O.nonlocal3d, (2, 16, 2, 4, 4), True)
+
+
+def test_attention3d_alone_through_the_gradient_penalty():
+    """The recorded adjoints of the grouped soft-max / batched GEMM / gamma * o + x (`SoftmaxG`, `BmmG`, `ScaleAddG`) on a group of
+    one: second-order gradients of x and of the five parameters, bounds of the recorded-backward convolution tests."""
+    from txt2vid_amd.models.layers import Attention3d
+    m, P = _seeded(lambda: Attention3d(16), 31, gamma=0.7)
+    x0 = rnd(32, 2, 16, 2, 4, 4)
+    x, xr = x0.to(DEV).requires_grad_(True), x0.clone().requires_grad_(True)
+    for out, leaf in ((m(x), x), (O.nonlocal3d(P, '', xr), xr)):
+        gx, = torch.autograd.grad(out.sum(), leaf, create_graph=True)
+        (gx ** 2).sum().backward()
+    close(x.grad, xr.grad, rtol=2e-4, atol=2e-4)
+    _grads_close(m, P, rtol=2e-4, atol=2e-4)
+
+
+@pytest.mark.parametrize('x_grad', [True, False])
+def test_attention2d_unfused_runs_the_grouped_ops(x_grad):
+    """The 2-D block with the fused attention kernel switched off: the `[b, C, 1, H, W]` view through the grouped ops, with an
+    input that takes part in the backward (forked: projections + residual) and one that does not."""
+    from txt2vid_amd.models.layers import Attention
+    _attention_first_order(Attention, O.nonlocal2d, (2, 16, 4, 4), x_grad, fused=False)
+
+
+@pytest.mark.parametrize('shape', [(2, 8, 2, 4, 4), (1, 8, 3, 5, 5)])             # the second: odd extents, padded pooling
+def test_down_block_alone_is_a_group_of_one(shape):
+    """`DownBlock(8, 16)(x)` is `down_block_levels(block, [x])[0]` bit for bit, and the block of the oracle (output, dL/dx, parameter
+    gradients; bounds of the fp32 convolution cases)."""
+    from txt2vid_amd.models.layers import DownBlock, down_block_levels
+    m, P = _seeded(lambda: DownBlock(8, 16), 41)
+    x0 = rnd(42, *shape)
+    x, xr = x0.to(DEV).requires_grad_(True), x0.clone().requires_grad_(True)
+    y, yr = m(x), O.down_block(P, '', xr)
+    assert torch.equal(y, down_block_levels(m, [x])[0])
+    close(y, yr, rtol=2e-4, atol=2e-4)
+    gy = rnd(43, *yr.shape)
+    (y * gy.to(DEV)).sum().backward()
+    (yr * gy).sum().backward()
+    close(x.grad, xr.grad, rtol=2e-4, atol=2e-4)
+    _grads_close(m, P, rtol=2e-4, atol=2e-4)
+
+
+@pytest.mark.parametrize('base', ['layers', 'nn'])
+def test_resnet3d_with_a_subclassed_pool(base):
+    """A one-block trunk whose `which_pool` is a trivial subclass: `(uncond, None, features)` and the input gradient against the
+    oracle, bounds of `test_resnet3d_and_gp`. A subclass of this package's `AvgPool3d` passes `forward_levels`' isinstance checks
+    (the fused stem); one of `torch.nn.AvgPool3d` is a foreign layer there and takes the plain arm, module by module."""
+    from txt2vid_amd.models import layers
+    from txt2vid_amd.models.resnet3d import Resnet3D
+
+    class Pool(layers.AvgPool3d if base == 'layers' else torch.nn.AvgPool3d):
+        pass
+    net, P = _seeded(lambda: Resnet3D(num_channels=1, num_down_blocks=1, with_attn=False, which_pool=Pool), 51)
+    x0 = rnd(52, 2, 1, 2, 8, 8)
+    x, xr = x0.to(DEV).requires_grad_(True), x0.clone().requires_grad_(True)
+    (u, c, feat), (ur, cr, featr) = net(x), O.resnet3d(P, xr, num_down_blocks=1, with_attn=False)
+    assert c is None and cr is None
+    close(u, ur)
+    close(feat, featr)
+    for a, b in ((u, feat), (ur, featr)):
+        ((a * rnd(22, 2, 1).to(a.device)).sum() + (b * rnd(23, 2, 128).to(a.device)).sum() * 1e-2).backward()
+    close(x.grad, xr.grad)
+
+
 @pytest.mark.parametrize('tag,cin,cout', [('ub', 16, 8), ('ub_same', 8, 8)])
 def test_up_block(golden, tag, cin, cout):
     from txt2vid_amd.models.layers import UpBlock

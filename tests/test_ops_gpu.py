@@ -970,8 +970,10 @@ def test_pyramid_gather():
 
 @pytest.mark.parametrize('ta,tb', [(False, False), (True, False), (False, True), (True, True)])
 def test_bmm_wide_tiles(ta, tb):
-    """The 16 x 64-tile batched GEMM (N >= 64, N % 4 == 0) against torch.bmm on the host for every transposition, with ragged
-    M / K (5, 33 rows; 4, 19, 70 deep) and N = 64, 100, 260; N = 66 keeps the 16 x 16 kernel."""
+    """Both batched GEMMs against torch.bmm on the host for every transposition, with ragged M / K (5, 33 rows; 4, 19, 70 deep)
+    and N = 64, 100, 260, 66: `TF.bmm` is a group of one on the grouped kernel (`T2V_MJ_BMM`: 64 x 64 tiles on the fp32 matrix
+    cores, edges zero-filled), `TF._bmm_raw` is the single-tensor `t2v_bmm` the text LSTM's weight gradient uses (16 x 64 tiles
+    where N >= 64 and N % 4 == 0; N = 66 keeps its 16 x 16 kernel)."""
     from txt2vid_amd import functional as TF
     gen = torch.Generator()
     gen.manual_seed(11)
@@ -981,6 +983,8 @@ def test_bmm_wide_tiles(ta, tb):
         want = torch.bmm(A.transpose(1, 2) if ta else A, B.transpose(1, 2) if tb else B)
         got = TF.bmm(A.to(dev()), B.to(dev()), ta, tb).cpu()
         np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=1e-5, atol=1e-5)
+        raw = TF._bmm_raw(A.to(dev()), B.to(dev()), M, N, K, ta, tb).cpu()
+        np.testing.assert_allclose(raw.numpy(), want.numpy(), rtol=1e-5, atol=1e-5)
 
 
 def _pool_ref(x, w, b, stem):

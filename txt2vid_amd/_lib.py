@@ -141,8 +141,6 @@ SIGNATURES = {
     't2v_relu_mask': [_P, _P, _P, _L, _P],
     't2v_add': [_P, _P, _P, _L, _P],
     't2v_axpby': [_F, _P, _F, _P, _P, _L, _P],
-    't2v_scale_dev': [_P, _F, _P, _P, _L, _P],
-    't2v_dot': [_P, _P, _P, _P, _L, _I, _P],
     't2v_fill': [_P, _F, _L, _P],
     't2v_tanh': [_P, _P, _L, _P],
     't2v_tanh_bwd': [_P, _P, _P, _L, _P],
@@ -150,9 +148,6 @@ SIGNATURES = {
     't2v_avgpool3d_bwd': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I3, _I3, _I3, _P],
     't2v_avgpool3d_multi': [_P, _I, _P],
     't2v_avgpool3d_bwd_multi': [_P, _I, _P],
-    't2v_maxpool2x2': [_P, _P, _P, _L, _I, _I, _P],
-    't2v_maxpool2x2_scatter': [_P, _P, _P, _L, _I, _I, _P],
-    't2v_maxpool2x2_gather': [_P, _P, _P, _L, _I, _I, _P],
     't2v_rowsum': [_P, _P, _L, _L, _P],
     't2v_rowbcast': [_P, _P, _L, _L, _P],
     't2v_upsample2x': [_P, _P, _L, _I, _I, _P],
@@ -184,9 +179,6 @@ SIGNATURES = {
     't2v_lstm_step_bwd_fused': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     't2v_lstm_pack_cols': [_P, _P, _I, _I, _P],
     't2v_bmm': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    't2v_softmax': [_P, _P, _L, _I, _P],
-    't2v_softmax_bwd': [_P, _P, _P, _L, _I, _P],
-    't2v_softmax_bwd_bwd_y': [_P, _P, _P, _P, _L, _I, _P],
     't2v_lstm_seq_step': [_P, _L, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _P],
     't2v_lstm_seq_step2': [_P, _P, _L, _L, _P, _I, _I, _P],
     't2v_lstm_train_step': [_P, _L, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _P],

@@ -48,10 +48,6 @@ __global__ void add_k(const float* a, const float* b, float* y, long n) { GRID_S
 __global__ void axpby_k(float al, const float* a, float be, const float* b, float* y, long n) {
     GRID_STRIDE(i, n) y[i] = al * a[i] + (b ? be * b[i] : 0.f);
 }
-__global__ void scale_dev_k(const float* s, float mul, const float* a, float* y, long n) {
-    const float f = s[0] * mul;
-    GRID_STRIDE(i, n) y[i] = f * a[i];
-}
 __global__ void fill_k(float* y, float v, long n) { GRID_STRIDE(i, n) y[i] = v; }
 __global__ void tanh_k(const float* x, float* y, long n) { GRID_STRIDE(i, n) y[i] = tanhf(x[i]); }
 __global__ void tanh_bwd_k(const float* g, const float* y, float* gx, long n) { GRID_STRIDE(i, n) gx[i] = g[i] * (1.f - y[i] * y[i]); }
@@ -76,11 +72,6 @@ extern "C" int t2v_axpby(float al, const float* a, float be, const float* b, flo
     T2V_LAUNCH(axpby_k, dim3(nblocks(n)), dim3(256), 0, S_(st), al, a, be, b, y, (long)n);
     return launch_status();
 }
-extern "C" int t2v_scale_dev(const float* s, float mul, const float* a, float* y, int64_t n, void* st) {
-    if (n <= 0) return n == 0 ? T2V_OK : T2V_EINVAL;
-    T2V_LAUNCH(scale_dev_k, dim3(nblocks(n)), dim3(256), 0, S_(st), s, mul, a, y, (long)n);
-    return launch_status();
-}
 extern "C" int t2v_fill(float* y, float v, int64_t n, void* st) {
     if (n <= 0) return n == 0 ? T2V_OK : T2V_EINVAL;
     T2V_LAUNCH(fill_k, dim3(nblocks(n)), dim3(256), 0, S_(st), y, v, (long)n);
@@ -94,29 +85,6 @@ extern "C" int t2v_tanh(const float* x, float* y, int64_t n, void* st) {
 extern "C" int t2v_tanh_bwd(const float* g, const float* y, float* gx, int64_t n, void* st) {
     if (n <= 0) return n == 0 ? T2V_OK : T2V_EINVAL;
     T2V_LAUNCH(tanh_bwd_k, dim3(nblocks(n)), dim3(256), 0, S_(st), g, y, gx, (long)n);
-    return launch_status();
-}
-
-// dot product, two deterministic stages: up to 256 workgroups leave partial sums in ws, one wave-pass sums them.
-__global__ __launch_bounds__(256) void dot_partial_k(const float* a, const float* b, float* ws, long n) {
-    __shared__ float red[4];
-    float acc = 0.f;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) acc += a[i] * b[i];
-    float s = block_sum(acc, red);
-    if (threadIdx.x == 0) ws[blockIdx.x] = s;
-}
-__global__ __launch_bounds__(256) void dot_final_k(const float* ws, float* out, int nb, int accum) {
-    __shared__ float red[4];
-    float acc = threadIdx.x < nb ? ws[threadIdx.x] : 0.f;
-    float s = block_sum(acc, red);
-    if (threadIdx.x == 0) out[0] = accum ? out[0] + s : s;
-}
-extern "C" int t2v_dot(const float* a, const float* b, float* out, float* ws, int64_t n, int accum, void* st) {
-    if (n <= 0 || !a || !b || !out || !ws) return T2V_EINVAL;
-    long nb = (n + 4095) / 4096;
-    if (nb > 256) nb = 256;
-    T2V_LAUNCH(dot_partial_k, dim3((unsigned)nb), dim3(256), 0, S_(st), a, b, ws, (long)n);
-    T2V_LAUNCH(dot_final_k, dim3(1), dim3(256), 0, S_(st), ws, out, (int)nb, accum);
     return launch_status();
 }
 
@@ -315,68 +283,6 @@ extern "C" int t2v_avgpool3d_bwd(const float* gy, float* gx, int NC, int D, int 
     const bool simple = p[0] == 0 && p[1] == 0 && p[2] == 0 && k[0] <= s[0] && k[1] <= s[1] && k[2] <= s[2];
     if (simple) T2V_LAUNCH(avgpool3d_bwd_simple_k, dim3(nblocks((long)NC * D * H * W)), dim3(256), 0, S_(st), gy, gx, NC, D, H, W, Do, Ho, Wo, q);
     else T2V_LAUNCH(avgpool3d_bwd_k, dim3(nblocks((long)NC * D * H * W)), dim3(256), 0, S_(st), gy, gx, NC, D, H, W, Do, Ho, Wo, q);
-    return launch_status();
-}
-
-// ---------------------------------------------------------------- 2x2 max-pool over (H,W) planes (floor)
-__global__ void maxpool2x2_k(const float* x, float* y, int32_t* idx, long planes, int H, int W) {
-    const int Ho = H / 2, Wo = W / 2;
-    const long n = planes * Ho * Wo;
-    GRID_STRIDE(i, n) {
-        int wo = i % Wo; long r = i / Wo;
-        int ho = r % Ho; long pl = r / Ho;
-        const float* px = x + pl * (long)H * W;
-        int best = (2 * ho) * W + 2 * wo;
-        float bv = px[best];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                int id = (2 * ho + a) * W + 2 * wo + b;
-                float v = px[id];
-                if (v > bv || (v != v && bv == bv)) { bv = v; best = id; }   // first max wins; NaN propagates
-            }
-        y[i] = bv;
-        idx[i] = best;
-    }
-}
-__global__ void maxpool2x2_scatter_k(const float* g, const int32_t* idx, float* gx, long planes, int H, int W) {
-    // every input element belongs to at most one window -> gather form, no atomics
-    const int Ho = H / 2, Wo = W / 2;
-    const long n = planes * H * W;
-    GRID_STRIDE(i, n) {
-        int w = i % W; long r = i / W;
-        int h = r % H; long pl = r / H;
-        int ho = h >> 1, wo = w >> 1;
-        float v = 0.f;
-        if (ho < Ho && wo < Wo) {
-            long o = (pl * Ho + ho) * Wo + wo;
-            if (idx[o] == h * W + w) v = g[o];
-        }
-        gx[i] = v;
-    }
-}
-__global__ void maxpool2x2_gather_k(const float* x, const int32_t* idx, float* y, long planes, int H, int W) {
-    const int Ho = H / 2, Wo = W / 2;
-    const long n = planes * Ho * Wo;
-    GRID_STRIDE(i, n) {
-        long pl = i / ((long)Ho * Wo);
-        y[i] = x[pl * (long)H * W + idx[i]];
-    }
-}
-extern "C" int t2v_maxpool2x2(const float* x, float* y, int32_t* idx, int64_t planes, int H, int W, void* st) {
-    if (!x || !y || !idx || planes < 1 || H < 2 || W < 2) return T2V_EINVAL;
-    T2V_LAUNCH(maxpool2x2_k, dim3(nblocks(planes * (H / 2) * (W / 2))), dim3(256), 0, S_(st), x, y, idx, (long)planes, H, W);
-    return launch_status();
-}
-extern "C" int t2v_maxpool2x2_scatter(const float* g, const int32_t* idx, float* gx, int64_t planes, int H, int W, void* st) {
-    if (!g || !gx || !idx || planes < 1 || H < 2 || W < 2) return T2V_EINVAL;
-    T2V_LAUNCH(maxpool2x2_scatter_k, dim3(nblocks(planes * H * W)), dim3(256), 0, S_(st), g, idx, gx, (long)planes, H, W);
-    return launch_status();
-}
-extern "C" int t2v_maxpool2x2_gather(const float* x, const int32_t* idx, float* y, int64_t planes, int H, int W, void* st) {
-    if (!x || !y || !idx || planes < 1 || H < 2 || W < 2) return T2V_EINVAL;
-    T2V_LAUNCH(maxpool2x2_gather_k, dim3(nblocks(planes * (H / 2) * (W / 2))), dim3(256), 0, S_(st), x, idx, y, (long)planes, H, W);
     return launch_status();
 }
 
@@ -1265,61 +1171,6 @@ extern "C" int t2v_bmm(const float* A, const float* B, float* C, int batch, int 
     }
     dim3 grid((N + 15) / 16, (M + 15) / 16, batch);
     T2V_LAUNCH(bmm_k, grid, dim3(256), 0, S_(st), A, B, C, M, N, K, ta, tb, accum);
-    return launch_status();
-}
-
-// softmax over the last dim: one wave per row, wavefront reductions
-__global__ __launch_bounds__(256) void softmax_k(const float* x, float* y, long rows, int n) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const float* p = x + row * n;
-    float mx = -INFINITY;
-    for (int i = lane; i < n; i += 64) mx = fmaxf(mx, p[i]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int i = lane; i < n; i += 64) s += expf(p[i] - mx);
-    s = wave_sum(s);
-    const float inv = 1.f / s;
-    for (int i = lane; i < n; i += 64) y[row * n + i] = expf(p[i] - mx) * inv;
-}
-__global__ __launch_bounds__(256) void softmax_bwd_k(const float* y, const float* gy, float* gx, long rows, int n) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const float* py = y + row * n;
-    const float* pg = gy + row * n;
-    float s = 0.f;
-    for (int i = lane; i < n; i += 64) s += pg[i] * py[i];
-    s = wave_sum(s);
-    for (int i = lane; i < n; i += 64) gx[row * n + i] = py[i] * (pg[i] - s);
-}
-__global__ __launch_bounds__(256) void softmax_bwd_bwd_y_k(const float* y, const float* gy, const float* gg, float* out, long rows, int n) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const float* py = y + row * n;
-    const float* pg = gy + row * n;
-    const float* pq = gg + row * n;
-    float s = 0.f, u = 0.f;
-    for (int i = lane; i < n; i += 64) { s += pg[i] * py[i]; u += pq[i] * py[i]; }
-    s = wave_sum(s);
-    u = wave_sum(u);
-    for (int i = lane; i < n; i += 64) out[row * n + i] = pq[i] * (pg[i] - s) - pg[i] * u;
-}
-extern "C" int t2v_softmax(const float* x, float* y, int64_t rows, int n, void* st) {
-    if (!x || !y || rows < 1 || n < 1) return T2V_EINVAL;
-    T2V_LAUNCH(softmax_k, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, S_(st), x, y, (long)rows, n);
-    return launch_status();
-}
-extern "C" int t2v_softmax_bwd(const float* y, const float* gy, float* gx, int64_t rows, int n, void* st) {
-    if (!y || !gy || !gx || rows < 1 || n < 1) return T2V_EINVAL;
-    T2V_LAUNCH(softmax_bwd_k, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, S_(st), y, gy, gx, (long)rows, n);
-    return launch_status();
-}
-extern "C" int t2v_softmax_bwd_bwd_y(const float* y, const float* gy, const float* gg, float* out, int64_t rows, int n, void* st) {
-    if (!y || !gy || !gg || !out || rows < 1 || n < 1) return T2V_EINVAL;
-    T2V_LAUNCH(softmax_bwd_bwd_y_k, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, S_(st), y, gy, gg, out, (long)rows, n);
     return launch_status();
 }
 

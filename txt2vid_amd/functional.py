@@ -11,6 +11,8 @@ these kernels (conv fwd <-> dgrad <-> wgrad form a closed triple).
 
 There is ONE convolution triple, the grouped one (`ConvG` / `ConvDgradG` / `ConvDgradMaskG` / `ConvWgradG` over
 `conv_group_raw` / `conv_group_wgrad_raw`): `conv`, `relu_conv` and `linear` on a single tensor are groups of one.
+Likewise the non-local block's small ops and the spatial sum (functional_multi.py): `bmm`, `softmax_lastdim`, `max_pool2x2`,
+`sum_spatial`, `scale_add` and `add_avg_pool3d` are the grouped Functions on a list of one.
 """
 import contextlib
 import ctypes as C
@@ -698,46 +700,31 @@ def _pool_out(n, k, s, p):
 
 
 class AvgPool3d(Function):
+    """pool(x), or with `x2` pool(x + x2) in the same kernel (DownBlock: DownSample(skip) + DownSample(main) ==
+    DownSample(skip + main))."""
+
     @staticmethod
-    def forward(ctx, x, k, s, p):
+    def forward(ctx, x, k, s, p, x2=None):
         x = _c(x)
         N, Cc, D, H, W = x.shape
         Do, Ho, Wo = _pool_out(D, k[0], s[0], p[0]), _pool_out(H, k[1], s[1], p[1]), _pool_out(W, k[2], s[2], p[2])
         ctx.cfg = (k, s, p, (D, H, W))
         y = torch.empty((N, Cc, Do, Ho, Wo), device=x.device, dtype=torch.float32)
         ka, sa, pa = _pool_args(k, s, p)
-        check(lib().t2v_avgpool3d(_p(x), None, _p(y), N * Cc, D, H, W, Do, Ho, Wo, ka, sa, pa, _stream()), 't2v_avgpool3d')
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        k, s, p, in_sp = ctx.cfg
-        return AvgPool3dBwd.apply(g, k, s, p, in_sp), None, None, None
-
-
-class AddAvgPool3d(Function):
-    """pool(a + b) in one kernel (DownBlock: DownSample(skip) + DownSample(main) == DownSample(skip + main))."""
-
-    @staticmethod
-    def forward(ctx, a, b, k, s, p):
-        a, b = _c(a), _c(b)
-        N, Cc, D, H, W = a.shape
-        Do, Ho, Wo = _pool_out(D, k[0], s[0], p[0]), _pool_out(H, k[1], s[1], p[1]), _pool_out(W, k[2], s[2], p[2])
-        ctx.cfg = (k, s, p, (D, H, W))
-        y = torch.empty((N, Cc, Do, Ho, Wo), device=a.device, dtype=torch.float32)
-        ka, sa, pa = _pool_args(k, s, p)
-        check(lib().t2v_avgpool3d(_p(a), _p(b), _p(y), N * Cc, D, H, W, Do, Ho, Wo, ka, sa, pa, _stream()), 't2v_avgpool3d')
+        x2 = _c(x2) if x2 is not None else None
+        check(lib().t2v_avgpool3d(_p(x), _p(x2), _p(y), N * Cc, D, H, W, Do, Ho, Wo, ka, sa, pa, _stream()), 't2v_avgpool3d')
         return y
 
     @staticmethod
     def backward(ctx, g):
         k, s, p, in_sp = ctx.cfg
         gx = AvgPool3dBwd.apply(g, k, s, p, in_sp)
-        return gx, gx, None, None, None
+        return gx, None, None, None, (gx if ctx.needs_input_grad[4] else None)
 
 
 def add_avg_pool3d(a, b, k, s, p=(0, 0, 0)):
-    return AddAvgPool3d.apply(a, b, tuple(k), tuple(s), tuple(p))
+    """pool(a + b) in one kernel (DownBlock: DownSample(skip) + DownSample(main) == DownSample(skip + main))."""
+    return avg_pool3d_group([a], [(k, s, p)], x2s=[b])[0]
 
 
 class AvgPool3dBwd(Function):
@@ -756,7 +743,7 @@ class AvgPool3dBwd(Function):
     @staticmethod
     def backward(ctx, gg):
         k, s, p = ctx.cfg
-        return AvgPool3d.apply(gg, k, s, p), None, None, None, None
+        return AvgPool3d.apply(gg, k, s, p, None), None, None, None, None
 
 
 def _pool_jobs(ins, in2s, outs, cfgs, in_sps, adds=None):
@@ -906,124 +893,24 @@ def avg_pool3d_group(xs, cfgs, x2s=None, adds=None):
     per-tensor launches for padded / overlapping windows (their adjoint is the general gather kernel)."""
     cfgs = tuple((tuple(k), tuple(s_), tuple(p)) for k, s_, p in cfgs)
     if any(any(p) or any(kk > ss for kk, ss in zip(k, s_)) for k, s_, p in cfgs) or len(xs) > 8:
-        if x2s is None:
-            ys = [avg_pool3d(x, *c) for x, c in zip(xs, cfgs)]
-        else:
-            ys = [add_avg_pool3d(x, x2, *c) for x, x2, c in zip(xs, x2s, cfgs)]
+        ys = [AvgPool3d.apply(x, *c, x2) for x, c, x2 in zip(xs, cfgs, x2s or [None] * len(xs))]
         return ys if adds is None else [add(y, a) for y, a in zip(ys, adds)]
     ts = list(xs) + (list(x2s) if x2s is not None else []) + (list(adds) if adds is not None else [])
     return list(AvgPool3dG.apply(cfgs, x2s is not None, adds is not None, *ts))
 
 
 def avg_pool3d(x, k, s, p=(0, 0, 0)):
-    return AvgPool3d.apply(x, tuple(k), tuple(s), tuple(p))
-
-
-class MaxPool2x2(Function):
-    """2x2 max-pool over the trailing (H,W) plane of any tensor (F.max_pool2d [2,2] / max_pool3d [1,2,2])."""
-
-    @staticmethod
-    def forward(ctx, x):
-        x = _c(x)
-        H, W = x.shape[-2], x.shape[-1]
-        planes = x.numel() // (H * W)
-        y = torch.empty(tuple(x.shape[:-2]) + (H // 2, W // 2), device=x.device, dtype=torch.float32)
-        idx = torch.empty(y.shape, device=x.device, dtype=torch.int32)
-        check(lib().t2v_maxpool2x2(_p(x), _p(y), _p(idx), planes, H, W, _stream()), 't2v_maxpool2x2')
-        ctx.save_for_backward(idx)
-        ctx.in_shape = tuple(x.shape)
-        ctx.mark_non_differentiable(idx)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        idx, = ctx.saved_tensors
-        return MaxScatter.apply(g, idx, ctx.in_shape)
-
-
-class MaxScatter(Function):
-    @staticmethod
-    def forward(ctx, g, idx, in_shape):
-        g = _c(g)
-        H, W = in_shape[-2], in_shape[-1]
-        planes = g.numel() // ((H // 2) * (W // 2))
-        gx = torch.empty(in_shape, device=g.device, dtype=torch.float32)
-        check(lib().t2v_maxpool2x2_scatter(_p(g), _p(idx), _p(gx), planes, H, W, _stream()), 't2v_maxpool2x2_scatter')
-        ctx.save_for_backward(idx)
-        ctx.in_shape = in_shape
-        return gx
-
-    @staticmethod
-    def backward(ctx, gg):
-        idx, = ctx.saved_tensors
-        return MaxGather.apply(gg, idx, ctx.in_shape), None, None
-
-
-class MaxGather(Function):
-    @staticmethod
-    def forward(ctx, x, idx, in_shape):
-        x = _c(x)
-        H, W = in_shape[-2], in_shape[-1]
-        planes = x.numel() // (H * W)
-        y = torch.empty(tuple(in_shape[:-2]) + (H // 2, W // 2), device=x.device, dtype=torch.float32)
-        check(lib().t2v_maxpool2x2_gather(_p(x), _p(idx), _p(y), planes, H, W, _stream()), 't2v_maxpool2x2_gather')
-        ctx.save_for_backward(idx)
-        ctx.in_shape = in_shape
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        idx, = ctx.saved_tensors
-        return MaxScatter.apply(g, idx, ctx.in_shape), None, None
+    return AvgPool3d.apply(x, tuple(k), tuple(s), tuple(p), None)
 
 
 def max_pool2x2(x):
-    return MaxPool2x2.apply(x)
-
-
-class RowSum(Function):
-    """[..., S] -> [...] : sum over the trailing flattened voxels (torch.sum(x,[2,3,4]))."""
-
-    @staticmethod
-    def forward(ctx, x, lead):
-        x = _c(x)
-        shp = tuple(x.shape)
-        rows = 1
-        for s in shp[:lead]:
-            rows *= s
-        S = x.numel() // rows
-        ctx.shape = shp
-        ctx.lead = lead
-        y = torch.empty(shp[:lead], device=x.device, dtype=torch.float32)
-        check(lib().t2v_rowsum(_p(x), _p(y), rows, S, _stream()), 't2v_rowsum')
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        return RowBcast.apply(g, ctx.shape, ctx.lead), None
-
-
-class RowBcast(Function):
-    @staticmethod
-    def forward(ctx, g, shape, lead):
-        g = _c(g)
-        rows = g.numel()
-        S = 1
-        for s in shape[lead:]:
-            S *= s
-        ctx.lead = lead
-        out = torch.empty(shape, device=g.device, dtype=torch.float32)
-        check(lib().t2v_rowbcast(_p(g), _p(out), rows, S, _stream()), 't2v_rowbcast')
-        return out
-
-    @staticmethod
-    def backward(ctx, gg):
-        return RowSum.apply(gg, ctx.lead), None, None
+    """2x2 max-pool over the trailing (H,W) plane of any tensor (F.max_pool2d [2,2] / max_pool3d [1,2,2])."""
+    return max_pool2x2_group([x])[0]
 
 
 def sum_spatial(x):
     """[b,C,T,H,W] -> [b,C]."""
-    return RowSum.apply(x, 2)
+    return sum_spatial_group([x])[0]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1038,83 +925,13 @@ def _bmm_raw(A, B, M, N, K, ta, tb):
     return out
 
 
-class Bmm(Function):
-    """C[b] = op(A[b]) @ op(B[b]); A stored [b,M,K] (ta=0) or [b,K,M] (ta=1); B [b,K,N] / [b,N,K]."""
-
-    @staticmethod
-    def forward(ctx, A, B, ta, tb):
-        M = A.shape[2] if ta else A.shape[1]
-        K = A.shape[1] if ta else A.shape[2]
-        N = B.shape[1] if tb else B.shape[2]
-        ctx.save_for_backward(A, B)
-        ctx.cfg = (ta, tb)
-        return _bmm_raw(A, B, M, N, K, ta, tb)
-
-    @staticmethod
-    def backward(ctx, G):
-        A, B = ctx.saved_tensors
-        ta, tb = ctx.cfg
-        dA = dB = None
-        if ctx.needs_input_grad[0]:
-            if not ta:
-                dA = Bmm.apply(G, B, False, not tb)          # [M,N] x B'^T
-            else:
-                dA = Bmm.apply(B, G, tb, True)               # B' x G^T  -> [K,M]
-        if ctx.needs_input_grad[1]:
-            if not tb:
-                dB = Bmm.apply(A, G, not ta, False)          # A'^T x G -> [K,N]
-            else:
-                dB = Bmm.apply(G, A, True, ta)               # G^T x A' -> [N,K]
-        return dA, dB, None, None
-
-
 def bmm(A, B, ta=False, tb=False):
-    return Bmm.apply(A, B, ta, tb)
-
-
-class Softmax(Function):
-    @staticmethod
-    def forward(ctx, x):
-        x = _c(x)
-        n = x.shape[-1]
-        y = torch.empty_like(x)
-        check(lib().t2v_softmax(_p(x), _p(y), x.numel() // n, n, _stream()), 't2v_softmax')
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        y, = ctx.saved_tensors
-        return SoftmaxBwd.apply(y, g)
-
-
-class SoftmaxBwd(Function):
-    @staticmethod
-    def forward(ctx, y, gy):
-        y, gy = _c(y), _c(gy)
-        n = y.shape[-1]
-        gx = torch.empty_like(y)
-        check(lib().t2v_softmax_bwd(_p(y), _p(gy), _p(gx), y.numel() // n, n, _stream()), 't2v_softmax_bwd')
-        ctx.save_for_backward(y, gy)
-        return gx
-
-    @staticmethod
-    def backward(ctx, gg):
-        y, gy = ctx.saved_tensors
-        gg = _c(gg)
-        n = y.shape[-1]
-        d_y = d_gy = None
-        if ctx.needs_input_grad[0]:
-            d_y = torch.empty_like(y)
-            check(lib().t2v_softmax_bwd_bwd_y(_p(y), _p(gy), _p(gg), _p(d_y), y.numel() // n, n, _stream()),
-                  't2v_softmax_bwd_bwd_y')
-        if ctx.needs_input_grad[1]:
-            d_gy = SoftmaxBwd.apply(y, gg)
-        return d_y, d_gy
+    """C[b] = op(A[b]) @ op(B[b]); A stored [b,M,K] (ta=0) or [b,K,M] (ta=1); B [b,K,N] / [b,N,K]."""
+    return bmm_group([A], [B], ta, tb)[0]
 
 
 def softmax_lastdim(x):
-    return Softmax.apply(x)
+    return softmax_lastdim_group([x])[0]
 
 
 class NonlocalAttend(Function):
@@ -1155,47 +972,9 @@ def nonlocal_attend(theta, phi, g):
     return NonlocalAttend.apply(theta, phi, g)
 
 
-class Dot(Function):
-    @staticmethod
-    def forward(ctx, a, b):
-        a, b = _c(a), _c(b)
-        ctx.save_for_backward(a, b)
-        out = torch.empty((), device=a.device, dtype=torch.float32)
-        ws = torch.empty((256,), device=a.device, dtype=torch.float32)
-        check(lib().t2v_dot(_p(a), _p(b), _p(out), _p(ws), a.numel(), 0, _stream()), 't2v_dot')
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        a, b = ctx.saved_tensors
-        return ScaleDev.apply(g, b), ScaleDev.apply(g, a)
-
-
-class ScaleDev(Function):
-    """y = s * a with s a 0-d device tensor (the non-local gain `gamma`)."""
-
-    @staticmethod
-    def forward(ctx, s, a):
-        a = _c(a)
-        ctx.save_for_backward(s, a)
-        y = torch.empty_like(a)
-        check(lib().t2v_scale_dev(_p(s), 1.0, _p(a), _p(y), a.numel(), _stream()), 't2v_scale_dev')
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        s, a = ctx.saved_tensors
-        gs = ga = None
-        if ctx.needs_input_grad[0]:
-            gs = Dot.apply(g, a)
-        if ctx.needs_input_grad[1]:
-            ga = ScaleDev.apply(s, g)
-        return gs, ga
-
-
 def scale_add(gamma, o, x):
     """gamma * o + x  (layers.py:36,68)."""
-    return Add.apply(ScaleDev.apply(gamma, o), x)
+    return scale_add_group(gamma, [o], [x])[0]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2069,12 +1848,6 @@ class GatherRows(Function):
         return GatherRows.apply(g, perm_dev, not ctx.inverse), None, None
 
 
-def gather_rows(x, perm):
-    import numpy as _np
-    perm_dev = torch.from_numpy(_np.ascontiguousarray(perm, dtype=_np.int32)).to(x.device)
-    return GatherRows.apply(x, perm_dev, False)
-
-
 _transposed_cache = {}
 
 
@@ -2406,45 +2179,6 @@ class CatBatch(Function):
 
 def cat_batch(a, b):
     return CatBatch.apply(a, b)
-
-
-class SplitRows(Function):
-    """(x[:n], x[n:]) of a dense tensor as views; the adjoint writes both gradients into ONE buffer (the native slices cost a
-    zero-fill + copy each and an accumulation: five launches per split in the backward)."""
-
-    @staticmethod
-    def forward(ctx, x, n):
-        x = _c(x)
-        ctx.n, ctx.shape = int(n), tuple(x.shape)
-        ctx.set_materialize_grads(False)
-        return x[:n], x[n:]
-
-    @staticmethod
-    def backward(ctx, ga, gb):
-        if ga is None and gb is None:
-            return None, None
-        if ga is not None and gb is not None:
-            return CatBatch.apply(ga, gb), None
-        out = torch.empty(ctx.shape, device=(ga if ga is not None else gb).device, dtype=torch.float32)
-        check(lib().t2v_fill(_p(out), 0.0, out.numel(), _stream()), 't2v_fill')
-        row = out.numel() // ctx.shape[0]
-        if ga is not None:
-            ga = _c(ga)
-            _copy2d(ga, 0, ga.numel(), out, 0, ga.numel(), 1, ga.numel())
-        else:
-            gb = _c(gb)
-            _copy2d(gb, 0, gb.numel(), out, ctx.n * row, gb.numel(), 1, gb.numel())
-        return out, None
-
-
-def split_rows(x, n):
-    """(x[:n], x[n:]) with a fused adjoint."""
-    return SplitRows.apply(x, n)
-
-
-def tail_rows(x, n_skip):
-    """x[n_skip:] — a trailing-rows slice of a contiguous tensor is a view."""
-    return x[n_skip:]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2967,10 +2701,6 @@ def conv_multi_group(xs, specs):
     return [list(out[k * n:(k + 1) * n]) for k in range(len(specs))]
 
 
-def conv_out_like(x, w):
-    return torch.empty((x.shape[0], w.shape[0]) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
-
-
 class ConvDgradG(Function):
     @staticmethod
     def forward(ctx, w, *gys):
@@ -3143,7 +2873,5 @@ def add_group(as_, bs):
     return list(AddG.apply(*(list(as_) + list(bs))))
 
 
-for _cls in (Relu, ReluMask, Add, AvgPool3d, AddAvgPool3d, AvgPool3dBwd, MaxPool2x2,
-             MaxScatter, MaxGather, RowSum, RowBcast, Bmm, Softmax, SoftmaxBwd, Dot, ScaleDev, CatFeatures, SliceCols,
-             EmbedCols, CatBatch, ConvWgradG):
+for _cls in (Relu, ReluMask, Add, AvgPool3d, AvgPool3dBwd, CatFeatures, SliceCols, EmbedCols, CatBatch, ConvWgradG):
     _pass_none_through(_cls)

@@ -1,6 +1,12 @@
-"""Grouped small ops of the non-local block and of the multi-level loss / gradient glue: one `t2v_multi` launch per op for
-all pyramid levels / members (include/t2v_hip.h, T2V_MJ_*). Part of the autograd surface `txt2vid_amd.functional`, which
-re-exports every name defined here; closed under differentiation like the single-tensor Functions."""
+"""The small ops of the non-local block (max-pool, batched GEMM, softmax, gamma * o + x), the trunk's spatial sum and the
+multi-level loss / gradient glue (add, fork, cat / slice): one `t2v_multi` launch per op for all pyramid levels / members
+(include/t2v_hip.h, T2V_MJ_*). These are the only Functions of those ops: a single tensor is a list of one
+(`functional.bmm`, `softmax_lastdim`, `max_pool2x2`, `sum_spatial`, `scale_add` wrap the `*_group` functions below). Part of the
+autograd surface `txt2vid_amd.functional`, which re-exports every name defined here.
+
+Closed under differentiation: every backward is written with Functions of this module (or views), so the gradient penalty's
+`autograd.grad(create_graph=True)` sweep and its second backward stay on these kernels. Members that receive no gradient
+(None) are left out of the backward launches."""
 import torch
 from torch.autograd import Function
 
@@ -8,9 +14,7 @@ from ._ops import lib, check, _c, _p, _stream
 
 
 # ------------------------------------------------------------------------------------------------
-# the non-local block's small ops over several tensors at once (`t2v_multi`): one launch per op for all pyramid
-# levels / members instead of one per level. Same closure under differentiation as the single-tensor Functions;
-# members that receive no gradient (None) are left out of the backward launches.
+# `t2v_multi`: up to 8 differently shaped jobs per launch, their descriptors in the kernel arguments
 # ------------------------------------------------------------------------------------------------
 (MJ_SCALE, MJ_SCALE_ADD, MJ_DOT, MJ_MAXPOOL, MJ_MAXSCATTER, MJ_MAXGATHER, MJ_SOFTMAX, MJ_SOFTMAX_BWD, MJ_SOFTMAX_BWD_BWD_Y, MJ_BMM,
  MJ_RELU_MASK, MJ_ROWSUM, MJ_ROWBCAST, MJ_ADD, MJ_CATLERP, MJ_CATCOLS, MJ_SLICECOLS, MJ_EMBEDCOLS) = range(1, 19)

@@ -92,55 +92,29 @@ class AvgPool3d(nn.Module):
         return TF.avg_pool3d(x, self.kernel_size, self.stride, self.padding)
 
 
-def _nonlocal(self, x, pooled_planes):
-    """Shared body of Attention / Attention3d (layers.py:23-36, 52-68)."""
-    b = x.size(0)
-    x_res = x
-    if x.dim() == 4 and x.is_cuda and x.requires_grad and torch.is_grad_enabled():
-        # the block's input feeds three projections and the residual: the projections run as ONE Function whose data gradients
-        # land in one buffer, and a grouped fork sums that with the residual's (else the autograd engine adds the four
-        # contributions with three ATen launches)
-        (xa,), (x_res,) = TF.fork_group([x])
-        w5 = [m.weight.unsqueeze(2) for m in (self.theta, self.phi, self.g)]
-        (theta,), (phi,), (g,) = TF.conv_multi_group([xa.unsqueeze(2)], [(w, None, False) for w in w5])
-        theta, phi, g = theta.squeeze(2), TF.max_pool2x2(phi.squeeze(2)), TF.max_pool2x2(g.squeeze(2))
-    else:
-        theta = self.theta(x)
-        phi = TF.max_pool2x2(self.phi(x))
-        g = TF.max_pool2x2(self.g(x))
-    theta = theta.reshape(b, self.ch // 8, -1)
-    phi = phi.reshape(b, self.ch // 8, -1)
-    g = g.reshape(b, self.ch // 2, -1)
-    if getattr(self, 'fused_attend', False) and TF.nonlocal_attend_ok(self.ch // 8, self.ch // 2):
-        # the generator's 2-D block: scores -> softmax -> weighted sum in one kernel, beta [b, N, N/4] never materialised
-        o = TF.nonlocal_attend(theta, phi, g)
-    else:
-        beta = TF.softmax_lastdim(TF.bmm(theta, phi, True, False))          # [b, N, N/4]
-        o = TF.bmm(g, beta, False, True)
-    o = o.reshape((b, self.ch // 2) + tuple(x.shape[2:]))
-    o = self.o(o)
-    return TF.scale_add(self.gamma, o, x_res)
-
-
-def nonlocal_levels(att, xs):
-    """Attention3d over a list of pyramid levels: the four 1x1x1 convolutions are grouped launches over the levels, and
+def nonlocal_levels(att, xs, attend=None):
+    """The non-local block (layers.py:23-36, 52-68) over a list of 5-D tensors, the pyramid levels of Attention3d or the one
+    `[b, C, 1, H, W]` view of the 2-D Attention's map: the four 1x1 convolutions are grouped launches over the levels, and
     so is every small op in between (max-pool, the two batched GEMMs, the softmax, gamma * o + x): 9 launches for all
-    levels together (layers.py:52-68)."""
+    levels together. `attend(theta, phi, g)`, where given, stands in for GEMM -> softmax -> GEMM of each level."""
     if len(xs) > 8:
         raise ValueError('at most 8 tensors per grouped non-local block')
     xs, xs_res = TF.fork_group(xs)           # projections + residual: their gradients are summed in one launch for all levels
-    thetas, phis, gs = TF.conv_multi_group(xs, [(att.theta.weight, None, False), (att.phi.weight, None, False),
-                                                (att.g.weight, None, False)])
+    # (the three projections run as ONE Function whose data gradients land in one buffer)
+    thetas, phis, gs = TF.conv_multi_group(xs, [(TF._as5(m.weight), None, False) for m in (att.theta, att.phi, att.g)])
     phis = TF.max_pool2x2_group(phis)
     gs = TF.max_pool2x2_group(gs)
     bs = [x.size(0) for x in xs]
     thetas = [t.reshape(b, att.ch // 8, -1) for t, b in zip(thetas, bs)]
     phis = [t.reshape(b, att.ch // 8, -1) for t, b in zip(phis, bs)]
     gs = [t.reshape(b, att.ch // 2, -1) for t, b in zip(gs, bs)]
-    betas = TF.softmax_lastdim_group(TF.bmm_group(thetas, phis, True, False))
-    os_ = TF.bmm_group(gs, betas, False, True)
+    if attend is not None:
+        os_ = [attend(t, p, g) for t, p, g in zip(thetas, phis, gs)]
+    else:
+        betas = TF.softmax_lastdim_group(TF.bmm_group(thetas, phis, True, False))          # [b, N, N/4] per level
+        os_ = TF.bmm_group(gs, betas, False, True)
     os_ = [o.reshape((b, att.ch // 2) + tuple(x.shape[2:])) for o, b, x in zip(os_, bs, xs)]
-    os_ = TF.conv_group(os_, att.o.weight, None)
+    os_ = TF.conv_group(os_, TF._as5(att.o.weight), None)
     return TF.scale_add_group(att.gamma, os_, xs_res)
 
 
@@ -160,7 +134,9 @@ class Attention(nn.Module):
         self.fused_attend = True          # first-order use only (generator): the fused kernel has no second-order adjoint
 
     def forward(self, x, y=None):
-        return _nonlocal(self, x, 2)
+        # the fused kernel: scores -> softmax -> weighted sum in one launch, beta [b, N, N/4] never materialised
+        fused = self.fused_attend and TF.nonlocal_attend_ok(self.ch // 8, self.ch // 2)
+        return nonlocal_levels(self, [x.unsqueeze(2)], attend=TF.nonlocal_attend if fused else None)[0].squeeze(2)
 
 
 class Attention3d(nn.Module):
@@ -178,7 +154,7 @@ class Attention3d(nn.Module):
         self.gamma = P(torch.tensor(0.), requires_grad=True)
 
     def forward(self, x, y=None):
-        return _nonlocal(self, x, 3)
+        return nonlocal_levels(self, [x])[0]
 
 
 class Identity(nn.Module):
@@ -289,14 +265,6 @@ def downsample_cfg(x):
     return k, s, p
 
 
-def downsample_sum(a, b):
-    """DownSample(a) + DownSample(b) == DownSample(a + b) (average pooling is linear): one fused kernel."""
-    k, s, p = downsample_cfg(a)
-    if k == [1, 1, 1]:
-        return TF.add(a, b)
-    return TF.add_avg_pool3d(a, b, k, s, p)
-
-
 class DownSample(nn.Module):
     """Average-pool by 2 every spatial/temporal dim of extent > 1 (pad 1 if odd) — layers.py:197-217."""
 
@@ -321,21 +289,9 @@ class DownBlock(nn.Module):
         self.main = ResidualBlock(inner_module=main, identity_map=ident)
 
     def forward(self, x):
-        m = self.main.inner_module
-        if isinstance(m[1], Conv3d) and isinstance(m[3], Conv3d):
-            idm = self.main.identity_map
-            if x.is_cuda and isinstance(idm[0], Conv3d):
-                return down_block_levels(self, [x])[0]             # a group of one: the same launches as the multi-level pass
-            h = TF.relu_conv(x, m[1].weight, m[1].bias)            # ReLU fused into the conv gather
-            if isinstance(idm[1], DownSample) and isinstance(m[4], DownSample) and TF.pool_conv_ok([h], m[3].weight, False):
-                # conv2 -> DownSample as ONE pooled convolution; the skip path's pooling adds it in its launch (as `down_block_levels`)
-                z = TF.pool_conv_group([h], m[3].weight, m[3].bias, relu_in=True, stem=False)[0]
-                s_ = idm[0](x)
-                return TF.avg_pool3d_group([s_], [downsample_cfg(s_)], adds=[z])[0]
-            h = TF.relu_conv(h, m[3].weight, m[3].bias)
-            if isinstance(idm[1], DownSample) and isinstance(m[4], DownSample):
-                return downsample_sum(idm[0](x), h)
-            return TF.add(idm(x), m[4](h))
+        m, idm = self.main.inner_module, self.main.identity_map
+        if isinstance(m[1], Conv3d) and isinstance(m[3], Conv3d) and isinstance(idm[0], Conv3d):
+            return down_block_levels(self, [x])[0]             # a group of one: the same launches as the multi-level pass
         return self.main(x)
 
 

@@ -30,20 +30,6 @@ class Resnet3D(nn.Module):
         if cond_dim > 0:
             self.fc = Linear(in_ch + cond_dim, 1)
 
-    def _stem(self, x):
-        """res_block (resnet3d.py:12-19) with the ReLU fused into the second convolution's gather."""
-        m = self.res_block.inner_module
-        if isinstance(m[0], Conv3d) and isinstance(m[2], Conv3d):
-            h = m[0](x)
-            if isinstance(m[3], AvgPool3d) and (m[3].kernel_size, m[3].stride, m[3].padding) == ((1, 2, 2), (2, 2, 2), (0, 0, 0)) and \
-                    TF.pool_conv_ok([h], m[2].weight, True):
-                # conv2 -> pooling as ONE pooled convolution (functional_pool.py), as in `forward_levels`
-                z = TF.pool_conv_group([h], m[2].weight, m[2].bias, relu_in=True, stem=True)[0]
-                return TF.add(self.res_block.identity_map(x), z)
-            h = TF.relu_conv(h, m[2].weight, m[2].bias)
-            return TF.add(self.res_block.identity_map(x), m[3](h))
-        return self.res_block(x)
-
     def groupable(self):
         m = self.res_block.inner_module
         return isinstance(m[0], Conv3d) and isinstance(m[2], Conv3d) and all(
@@ -119,14 +105,14 @@ class Resnet3D(nn.Module):
 
     def forward(self, x=None, cond=None, xbar=None, computed_features=None):
         uncond = None
-        if computed_features is None and x is not None and x.is_cuda and self.groupable():
+        if computed_features is None and x is not None and self.groupable():
             # one tensor = a group of one: the same launches and the same fused adjoints (forked inputs, conv1 + skip in one
             # Function, grouped non-local block) as the multi-level pass
             return self.forward_levels([x], [cond] if cond is not None else None)[0]
         if computed_features is not None:
             x = computed_features
         else:
-            x = self._stem(x)
+            x = self.res_block(x)           # a trunk built from foreign layers: the plain module composition
             for d in self.down:
                 x = d(x)
             x = TF.sum_spatial(x)                           # torch.sum(x, [2,3,4])  (resnet3d.py:48)
