@@ -216,16 +216,18 @@ int t2v_fill(float* y, float v, int64_t n, void* stream);
 int t2v_tanh(const float* x, float* y, int64_t n, void* stream);                 /* layers.py:258    */
 int t2v_tanh_bwd(const float* g, const float* y, float* gx, int64_t n, void* stream);
 
-/* avg_pool3d with per-dim kernel/stride/pad, count_include_pad=True (layers.py:217, resnet3d.py:16).
- * bwd scatters g/(kd*kh*kw) back (windows never overlap on this path: stride >= kernel). */
-/* x2 != NULL: y = pool(x + x2) — the residual add fused into the block's DownSample (layers.py:93-96,217). */
+/* avg_pool3d with per-dim kernel (<= 4) / stride / pad, count_include_pad=True (layers.py:217, resnet3d.py:16), and its
+ * adjoint gx = pool^T(gy). Each is t2v_avgpool3d(_bwd)_multi below on one job.
+ * x2 != NULL: y = pool(x + x2) — the residual add fused into the block's DownSample (layers.py:93-96,217). */
 int t2v_avgpool3d(const float* x, const float* x2, float* y, int NC, int D, int H, int W, int Do, int Ho, int Wo,
                   const int32_t k[3], const int32_t s[3], const int32_t p[3], void* stream);
 int t2v_avgpool3d_bwd(const float* gy, float* gx, int NC, int D, int H, int W, int Do, int Ho, int Wo,
                       const int32_t k[3], const int32_t s[3], const int32_t p[3], void* stream);
 /* Multi-tensor forms: `jobs` is a HOST array; 8 jobs per launch, descriptors passed in the kernel arguments (the pyramid
    levels of one DownBlock are pooled together). fwd: y = pool(x [+ x2]) [+ add]. bwd: x = dL/dy [NC,Do,Ho,Wo], y = dL/dx
-   [NC,D,H,W]; only un-padded windows with kernel <= stride (what DownSample produces, layers.py:197-217). */
+   [NC,D,H,W]. Un-padded windows with kernel <= stride (what DownSample produces at even extents, layers.py:197-217) take
+   one read per voxel; a launch that holds a padded or overlapping job gathers for that job and keeps the one-read form for
+   the others. */
 typedef struct t2v_pool_job {
     const float* x; const float* x2; float* y;
     const float* add;    /* optional. fwd: y = pool(x [+ x2]) + add  (add has y's shape: the stem's skip, resnet3d.py:16-19);

@@ -59,10 +59,10 @@ def test_conv_fwd_bwd(xs, cout, k):
 
 @pytest.mark.parametrize('xs,cout,k', [((2, 24, 3, 6, 5), 40, (3, 3, 3)), ((7, 48), 20, (1, 1, 1))])
 def test_single_tensor_entry_points_equal_a_group_of_one(xs, cout, k):
-    """The single-tensor C entry points (`t2v_conv_fwd`, `t2v_conv_wgrad`, `t2v_channel_sum` and their size queries), which
-    the Python package no longer calls, against the grouped launchers on a one-member list: bit for bit, because the C
-    wrappers forward to the same functions with the same arguments (the channel sum walks the same elements in the same
-    order). fp32 only: the single entry points have no bf16 form."""
+    """The single-tensor C entry points (`t2v_conv_fwd`, `t2v_conv_wgrad`, `t2v_channel_sum` and their size queries,
+    `t2v_avgpool3d` and `t2v_avgpool3d_bwd`), which the Python package no longer calls, against the grouped launchers on a
+    one-member list: bit for bit, because the C wrappers forward to the same functions with the same arguments (the channel
+    sum walks the same elements in the same order). fp32 only: the single entry points have no bf16 form."""
     import ctypes as C
     from txt2vid_amd import functional as TF
     from txt2vid_amd._lib import lib
@@ -98,6 +98,22 @@ def test_single_tensor_entry_points_equal_a_group_of_one(xs, cout, k):
     db = torch.empty((cout,), device=dev())
     assert lib().t2v_channel_sum(p(gy), p(db), p(buf(ncs)), N, cout, S, 0, st()) == 0
     assert torch.equal(db, TF.channel_sum_group_raw([gy]))
+
+    I3 = C.c_int32 * 3
+    for shape, cfg in (((2, 3, 4, 6, 6), ((2, 2, 2), (2, 2, 2), (0, 0, 0))), ((2, 3, 3, 5, 7), ((2, 2, 2), (2, 2, 2), (1, 1, 1)))):
+        px = rnd(5, *shape).to(dev()).requires_grad_(True)
+        px2 = rnd(6, *shape).to(dev())
+        yp = TF.avg_pool3d(px, *cfg)
+        gyp = rnd(7, *yp.shape).to(dev())
+        dims = (shape[0] * shape[1],) + tuple(shape[2:]) + tuple(yp.shape[2:])
+        k3, s3, p3 = (I3(*v) for v in cfg)
+        for second, want in ((None, yp), (px2, TF.add_avg_pool3d(px, px2, *cfg))):
+            yc = torch.empty_like(yp)
+            assert lib().t2v_avgpool3d(p(px), p(second), p(yc), *dims, k3, s3, p3, st()) == 0
+            assert torch.equal(yc, want)
+        gxc = torch.empty(shape, device=dev())
+        assert lib().t2v_avgpool3d_bwd(p(gyp), p(gxc), *dims, k3, s3, p3, st()) == 0
+        assert torch.equal(gxc, torch.autograd.grad(yp, px, gyp)[0])
 
 
 @pytest.mark.parametrize('case', GROUPED_CASES, ids=[c[0] for c in GROUPED_CASES])
@@ -398,7 +414,9 @@ def test_avgpool():
     from txt2vid_amd import functional as TF
     for shape, k, s, p in (((2, 3, 4, 6, 6), (1, 2, 2), (2, 2, 2), (0, 0, 0)),
                            ((2, 3, 3, 5, 7), (2, 2, 2), (2, 2, 2), (1, 1, 1)),
-                           ((1, 2, 1, 4, 1), (1, 2, 1), (1, 2, 1), (0, 0, 0))):
+                           ((1, 2, 1, 4, 1), (1, 2, 1), (1, 2, 1), (0, 0, 0)),
+                           ((1, 2, 4, 5, 6), (2, 3, 3), (1, 2, 2), (0, 1, 1)),          # overlapping and padded
+                           ((2, 2, 3, 6, 5), (1, 3, 3), (1, 2, 2), (0, 0, 0))):         # kernel > stride, no padding
         x = rnd(1, *shape)
         xr = x.clone().requires_grad_(True)
         yr = F.avg_pool3d(xr, k, s, p)
@@ -411,13 +429,10 @@ def test_avgpool():
         close(xd.grad, xr.grad)
 
 
-def test_avgpool_group_matches_torch_first_and_second_order():
-    """Multi-tensor pooling (`t2v_avgpool3d_multi` / `_bwd_multi`): pool(x + x2) + add over four differently shaped
-    members, incl. the stem's kernel (1,2,2) / stride 2 and an identity member; gradients of a GP-shaped loss."""
+def _avgpool_group_first_and_second_order(shapes, cfgs):
+    """One `avg_pool3d_group` call, pool(x + x2) + add, against torch in float64: values, and the gradients of a GP-shaped loss
+    (y**3, its `create_graph` gradients squared) with respect to every input."""
     from txt2vid_amd import functional as TF
-    shapes = [(2, 3, 4, 8, 8), (1, 3, 2, 6, 4), (3, 3, 1, 4, 4), (2, 3, 1, 1, 1)]
-    cfgs = [((2, 2, 2), (2, 2, 2), (0, 0, 0)), ((1, 2, 2), (2, 2, 2), (0, 0, 0)), ((1, 2, 2), (1, 2, 2), (0, 0, 0)),
-            ((1, 1, 1), (1, 1, 1), (0, 0, 0))]
     xs0 = [rnd(30 + i, *s) for i, s in enumerate(shapes)]
     x2s0 = [rnd(40 + i, *s) for i, s in enumerate(shapes)]
 
@@ -441,6 +456,73 @@ def test_avgpool_group_matches_torch_first_and_second_order():
     got = run(lambda xs, x2s, adds: TF.avg_pool3d_group(xs, cfgs, x2s=x2s, adds=adds), lambda t: t.to(dev()))
     for a, r in zip(got, ref):
         close(a, r.float(), rtol=1e-4, atol=1e-4)
+
+
+def test_avgpool_group_matches_torch_first_and_second_order():
+    """Multi-tensor pooling (`t2v_avgpool3d_multi` / `_bwd_multi`): pool(x + x2) + add over four differently shaped
+    members, incl. the stem's kernel (1,2,2) / stride 2 and an identity member; gradients of a GP-shaped loss."""
+    _avgpool_group_first_and_second_order(
+        [(2, 3, 4, 8, 8), (1, 3, 2, 6, 4), (3, 3, 1, 4, 4), (2, 3, 1, 1, 1)],
+        [((2, 2, 2), (2, 2, 2), (0, 0, 0)), ((1, 2, 2), (2, 2, 2), (0, 0, 0)), ((1, 2, 2), (1, 2, 2), (0, 0, 0)),
+         ((1, 1, 1), (1, 1, 1), (0, 0, 0))])
+
+
+def test_avgpool_group_of_mixed_windows_first_and_second_order():
+    """One launch each way over two one-read members ((2,2,2) / 2 and the stem's (1,2,2) / 2), an overlapping and padded
+    member and a kernel > stride member: the adjoint's gather form and its one-read form side by side in one batch, and the
+    recorded backward through `AvgPool3dBwdG` with such windows."""
+    _avgpool_group_first_and_second_order(
+        [(2, 3, 4, 8, 8), (1, 3, 2, 6, 4), (1, 2, 4, 5, 6), (2, 2, 3, 6, 5)],
+        [((2, 2, 2), (2, 2, 2), (0, 0, 0)), ((1, 2, 2), (2, 2, 2), (0, 0, 0)), ((2, 3, 3), (1, 2, 2), (0, 1, 1)),
+         ((1, 3, 3), (1, 2, 2), (0, 0, 0))])
+
+
+def test_avgpool_group_of_more_members_than_one_launch_takes():
+    """Nine members: the launcher's second batch (a one-read member alone), and a padded member among the first eight."""
+    from txt2vid_amd import functional as TF
+    cfgs = [((2, 2, 2), (2, 2, 2), (1, 1, 1) if i == 3 else (0, 0, 0)) for i in range(9)]
+    xs0 = [rnd(60 + i, 1, 2, 2, 4, 4) for i in range(9)]
+    xr = [x.double().requires_grad_(True) for x in xs0]
+    yr = [F.avg_pool3d(x, *c) for x, c in zip(xr, cfgs)]
+    gys = [rnd(70 + i, *y.shape) for i, y in enumerate(yr)]
+    sum((y * g.double()).sum() for y, g in zip(yr, gys)).backward()
+    xd = [x.to(dev()).requires_grad_(True) for x in xs0]
+    yd = TF.avg_pool3d_group(xd, cfgs)
+    sum((y * g.to(dev())).sum() for y, g in zip(yd, gys)).backward()
+    for y, r, x, xg in zip(yd, yr, xd, xr):
+        close(y, r.float())
+        close(x.grad, xg.grad.float())
+
+
+@pytest.mark.parametrize('arm', ['both', 'alias_unused', 'pooled_unused', 'recorded'])
+def test_fork_pool_group_backward_arms(arm):
+    """`ForkPoolG.backward`: x feeds x * c and pool(x), one one-read member and one padded. both: the adjoint adds the alias'
+    gradient in its own launch (`t2v_pool_job.add`); one output unused: its gradient is None; recorded: the composed arm
+    under `create_graph`, then a second backward."""
+    from txt2vid_amd import functional as TF
+    shapes = [(2, 3, 4, 6, 6), (2, 3, 3, 5, 7)]
+    cfgs = [((2, 2, 2), (2, 2, 2), (0, 0, 0)), ((2, 2, 2), (2, 2, 2), (1, 1, 1))]
+    xs0 = [rnd(80 + i, *s) for i, s in enumerate(shapes)]
+    cs0 = [rnd(82 + i, *s) for i, s in enumerate(shapes)]
+
+    def run(fork_pool, to):
+        xs = [to(x).requires_grad_(True) for x in xs0]
+        xa, yp = fork_pool(xs)
+        out = 0
+        if arm != 'alias_unused':
+            out = out + sum(((a * to(c)) ** 3).sum() for a, c in zip(xa, cs0))
+        if arm != 'pooled_unused':
+            out = out + sum((y ** 3).sum() for y in yp)
+        if arm == 'recorded':
+            g1 = torch.autograd.grad(out, xs, create_graph=True)
+            out = out + sum((g * g).sum() for g in g1)
+        out.backward()
+        return [y.detach() for y in yp] + [x.grad for x in xs]
+
+    ref = run(lambda xs: (xs, [F.avg_pool3d(x, *c) for x, c in zip(xs, cfgs)]), lambda t: t.double())
+    got = run(lambda xs: TF.fork_pool_group(xs, cfgs), lambda t: t.to(dev()))
+    for a, r in zip(got, ref):
+        close(a, r.float())
 
 
 def test_maxpool_softmax_bmm_double_backward():

@@ -89,91 +89,18 @@ extern "C" int t2v_tanh_bwd(const float* g, const float* y, float* gx, int64_t n
 }
 
 // ---------------------------------------------------------------- avg-pool (count_include_pad)
-struct Pool3 { int k[3], s[3], p[3]; };
-
-// x2 != nullptr: y = pool(x + x2) (the residual add of DownBlock fused into its DownSample: pooling is linear)
-__global__ void avgpool3d_k(const float* x, const float* x2, float* y, int NC, int D, int H, int W, int Do, int Ho, int Wo, Pool3 q) {
-    const long n = (long)NC * Do * Ho * Wo;
-    const float inv = 1.f / (float)(q.k[0] * q.k[1] * q.k[2]);
-    GRID_STRIDE(i, n) {
-        int wo = i % Wo; long r = i / Wo;
-        int ho = r % Ho; r /= Ho;
-        int d_o = r % Do; long nc = r / Do;
-        const float* px = x + nc * (long)D * H * W;
-        const float* px2 = x2 ? x2 + nc * (long)D * H * W : nullptr;
-        float acc = 0.f;
-        for (int a = 0; a < q.k[0]; ++a) {
-            int d = d_o * q.s[0] - q.p[0] + a;
-            if ((unsigned)d >= (unsigned)D) continue;
-            for (int b = 0; b < q.k[1]; ++b) {
-                int h = ho * q.s[1] - q.p[1] + b;
-                if ((unsigned)h >= (unsigned)H) continue;
-                for (int c = 0; c < q.k[2]; ++c) {
-                    int w = wo * q.s[2] - q.p[2] + c;
-                    if ((unsigned)w >= (unsigned)W) continue;
-                    const long o = ((long)d * H + h) * W + w;
-                    acc += px2 ? px[o] + px2[o] : px[o];
-                }
-            }
-        }
-        y[i] = acc * inv;
-    }
-}
-// adjoint (gather form): gx[d,h,w] = sum over windows containing it of gy/vol. stride >= kernel on this
-// path, but the general overlap case is handled as well.
-__global__ void avgpool3d_bwd_k(const float* gy, float* gx, int NC, int D, int H, int W, int Do, int Ho, int Wo, Pool3 q) {
-    const long n = (long)NC * D * H * W;
-    const float inv = 1.f / (float)(q.k[0] * q.k[1] * q.k[2]);
-    GRID_STRIDE(i, n) {
-        int w = i % W; long r = i / W;
-        int h = r % H; r /= H;
-        int d = r % D; long nc = r / D;
-        const float* pg = gy + nc * (long)Do * Ho * Wo;
-        float acc = 0.f;
-        for (int a = 0; a < q.k[0]; ++a) {
-            int td = d + q.p[0] - a;
-            if (td < 0 || td % q.s[0]) continue;
-            int d_o = td / q.s[0];
-            if (d_o >= Do) continue;
-            for (int b = 0; b < q.k[1]; ++b) {
-                int th = h + q.p[1] - b;
-                if (th < 0 || th % q.s[1]) continue;
-                int ho = th / q.s[1];
-                if (ho >= Ho) continue;
-                for (int c = 0; c < q.k[2]; ++c) {
-                    int tw = w + q.p[2] - c;
-                    if (tw < 0 || tw % q.s[2]) continue;
-                    int wo = tw / q.s[2];
-                    if (wo >= Wo) continue;
-                    acc += pg[((long)d_o * Ho + ho) * Wo + wo];
-                }
-            }
-        }
-        gx[i] = acc * inv;
-    }
-}
-// non-overlapping, unpadded windows (kernel <= stride, the only kind on the hot path): every input voxel belongs
-// to at most one window -> one read, no divisibility tests
-__global__ void avgpool3d_bwd_simple_k(const float* gy, float* gx, int NC, int D, int H, int W, int Do, int Ho, int Wo, Pool3 q) {
-    const long n = (long)NC * D * H * W;
-    const float inv = 1.f / (float)(q.k[0] * q.k[1] * q.k[2]);
-    GRID_STRIDE(i, n) {
-        int w = i % W; long r = i / W;
-        int h = r % H; r /= H;
-        int d = r % D; long nc = r / D;
-        const int d_o = d / q.s[0], ho = h / q.s[1], wo = w / q.s[2];
-        const bool in = (d - d_o * q.s[0] < q.k[0]) && (h - ho * q.s[1] < q.k[1]) && (w - wo * q.s[2] < q.k[2]) &&
-                        d_o < Do && ho < Ho && wo < Wo;
-        gx[i] = in ? gy[((nc * Do + d_o) * Ho + ho) * (long)Wo + wo] * inv : 0.f;
-    }
-}
 // Multi-tensor forms (the pyramid levels of one DownBlock pooled by ONE launch): up to 8 jobs by value in the kernel
-// arguments; a workgroup handles 1024 consecutive output elements of one job.
+// arguments; a workgroup handles POOL_CHUNK consecutive output elements of one job.
+// fwd: y = pool(x [+ x2]) [+ add]  (x2: the residual add of DownBlock fused into its DownSample: pooling is linear)
 #define POOL_MT 8
 #ifndef POOL_CHUNK
 #define POOL_CHUNK 512           // (512 vs 1024: -0.12 ms per iteration: the small members of a launch get more workgroups in flight; 256: the same)
 #endif
 struct PoolBatch { t2v_pool_job j[POOL_MT]; int begin[POOL_MT + 1]; int n; };
+// padded or overlapping windows: the adjoint needs the gather form
+__host__ __device__ static inline bool pool_general(const t2v_pool_job& q) {
+    return q.p[0] != 0 || q.p[1] != 0 || q.p[2] != 0 || q.k[0] > q.s[0] || q.k[1] > q.s[1] || q.k[2] > q.s[2];
+}
 __global__ __launch_bounds__(256) void avgpool3d_multi_k(const PoolBatch tb) {
     int ji = 0;
 #pragma unroll
@@ -209,7 +136,38 @@ __global__ __launch_bounds__(256) void avgpool3d_multi_k(const PoolBatch tb) {
         q.y[i] = acc * inv + (q.add ? q.add[i] : 0.f);
     }
 }
-// adjoint for non-overlapping unpadded windows (what DownSample produces): job.x = dL/dy [NC,Do,Ho,Wo], job.y = dL/dx
+// adjoint of a padded or overlapping window (gather form): dL/dx[d,h,w] = sum over the windows containing it of dL/dy / vol.
+// The product is rounded on its own, not fused with the job's `add`: dL/dx then has the bits of a separate add of the two
+// gradients, the same for a forked input as for any other tensor with two consumers.
+__device__ __forceinline__ float pool_gather(const t2v_pool_job& q, const float* pg, int d, int h, int w, float inv) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+    for (int a = 0; a < q.k[0]; ++a) {
+        int td = d + q.p[0] - a;
+        if (td < 0 || td % q.s[0]) continue;
+        int d_o = td / q.s[0];
+        if (d_o >= q.Do) continue;
+        for (int b = 0; b < q.k[1]; ++b) {
+            int th = h + q.p[1] - b;
+            if (th < 0 || th % q.s[1]) continue;
+            int ho = th / q.s[1];
+            if (ho >= q.Ho) continue;
+            for (int c = 0; c < q.k[2]; ++c) {
+                int tw = w + q.p[2] - c;
+                if (tw < 0 || tw % q.s[2]) continue;
+                int wo = tw / q.s[2];
+                if (wo >= q.Wo) continue;
+                acc += pg[((long)d_o * q.Ho + ho) * q.Wo + wo];
+            }
+        }
+    }
+    return acc * inv;
+}
+// adjoint: job.x = dL/dy [NC,Do,Ho,Wo], job.y = dL/dx. Non-overlapping unpadded windows (kernel <= stride: what DownSample
+// produces at even extents, the only kind on the hot path): every input voxel belongs to at most one window -> one read, no
+// divisibility tests. GENERAL: a batch in which some job has padded or overlapping windows; such a job gathers, the others
+// keep the one-read formula (a job-uniform branch), so a job's bits do not depend on its neighbours in the batch.
+template <bool GENERAL>
 __global__ __launch_bounds__(256) void avgpool3d_bwd_multi_k(const PoolBatch tb) {
     int ji = 0;
 #pragma unroll
@@ -221,14 +179,20 @@ __global__ __launch_bounds__(256) void avgpool3d_bwd_multi_k(const PoolBatch tb)
     const float inv = 1.f / (float)(q.k[0] * q.k[1] * q.k[2]);
     const long base = (long)((int)blockIdx.x - tb.begin[ji]) * POOL_CHUNK;
     const float* __restrict__ gy = q.x;
+    const bool gather = GENERAL && pool_general(q);
     for (long i = base + threadIdx.x; i < base + POOL_CHUNK && i < n; i += 256) {
         int w = i % W; long r = i / W;
         int h = r % H; r /= H;
         int d = r % D; long nc = r / D;
-        const int d_o = d / q.s[0], ho = h / q.s[1], wo = w / q.s[2];
-        const bool in = (d - d_o * q.s[0] < q.k[0]) && (h - ho * q.s[1] < q.k[1]) && (w - wo * q.s[2] < q.k[2]) &&
-                        d_o < Do && ho < Ho && wo < Wo;
-        const float v = in ? gy[((nc * Do + d_o) * Ho + ho) * (long)Wo + wo] * inv : 0.f;
+        float v;
+        if (gather) {
+            v = pool_gather(q, gy + nc * (long)Do * Ho * Wo, d, h, w, inv);
+        } else {
+            const int d_o = d / q.s[0], ho = h / q.s[1], wo = w / q.s[2];
+            const bool in = (d - d_o * q.s[0] < q.k[0]) && (h - ho * q.s[1] < q.k[1]) && (w - wo * q.s[2] < q.k[2]) &&
+                            d_o < Do && ho < Ho && wo < Wo;
+            v = in ? gy[((nc * Do + d_o) * Ho + ho) * (long)Wo + wo] * inv : 0.f;
+        }
         q.y[i] = q.add ? v + q.add[i] : v;          // (add: dL/dx's other contribution, same shape as dL/dx — a forked block input)
     }
 }
@@ -238,13 +202,13 @@ static int pool_multi(const t2v_pool_job* jobs, int njobs, bool bwd, void* st) {
         PoolBatch tb;
         const int cnt = njobs - at < POOL_MT ? njobs - at : POOL_MT;
         long blocks = 0;
+        bool general = false;
         for (int i = 0; i < cnt; ++i) {
             const t2v_pool_job& q = jobs[at + i];
             if (!q.x || !q.y || q.NC < 1 || q.D < 1 || q.H < 1 || q.W < 1 || q.Do < 1 || q.Ho < 1 || q.Wo < 1) return T2V_EINVAL;
-            for (int a = 0; a < 3; ++a) {
+            for (int a = 0; a < 3; ++a)
                 if (q.k[a] < 1 || q.k[a] > 4 || q.s[a] < 1 || q.p[a] < 0) return T2V_EINVAL;
-                if (bwd && (q.p[a] != 0 || q.k[a] > q.s[a])) return T2V_EINVAL;      // the simple adjoint only
-            }
+            general |= pool_general(q);
             tb.j[i] = q;
             tb.begin[i] = (int)blocks;
             const long n = bwd ? (long)q.NC * q.D * q.H * q.W : (long)q.NC * q.Do * q.Ho * q.Wo;
@@ -254,36 +218,28 @@ static int pool_multi(const t2v_pool_job* jobs, int njobs, bool bwd, void* st) {
         for (int i = cnt; i < POOL_MT; ++i) tb.j[i] = tb.j[0];
         tb.n = cnt;
         if (blocks > 0x7fffffffL) return T2V_EINVAL;
-        if (bwd) T2V_LAUNCH(avgpool3d_bwd_multi_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
-        else T2V_LAUNCH(avgpool3d_multi_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
+        if (!bwd) T2V_LAUNCH(avgpool3d_multi_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
+        else if (general) T2V_LAUNCH(avgpool3d_bwd_multi_k<true>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
+        else T2V_LAUNCH(avgpool3d_bwd_multi_k<false>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
     }
     return launch_status();
 }
 extern "C" int t2v_avgpool3d_multi(const t2v_pool_job* jobs, int njobs, void* st) { return pool_multi(jobs, njobs, false, st); }
 extern "C" int t2v_avgpool3d_bwd_multi(const t2v_pool_job* jobs, int njobs, void* st) { return pool_multi(jobs, njobs, true, st); }
 
-static bool pool_ok(const int32_t* k, const int32_t* s, const int32_t* p) {
-    for (int i = 0; i < 3; ++i)
-        if (k[i] < 1 || k[i] > 4 || s[i] < 1 || p[i] < 0) return false;
-    return true;
+// the single-tensor entry points: a group of one
+static int pool_single(const float* in, const float* x2, float* out, int NC, int D, int H, int W, int Do, int Ho, int Wo,
+                       const int32_t k[3], const int32_t s[3], const int32_t p[3], bool bwd, void* st) {
+    t2v_pool_job q = {in, x2, out, nullptr, NC, D, H, W, Do, Ho, Wo, {k[0], k[1], k[2]}, {s[0], s[1], s[2]}, {p[0], p[1], p[2]}};
+    return pool_multi(&q, 1, bwd, st);
 }
 extern "C" int t2v_avgpool3d(const float* x, const float* x2, float* y, int NC, int D, int H, int W, int Do, int Ho, int Wo,
                              const int32_t k[3], const int32_t s[3], const int32_t p[3], void* st) {
-    if (!x || !y || NC < 1 || !pool_ok(k, s, p)) return T2V_EINVAL;
-    Pool3 q;
-    for (int i = 0; i < 3; ++i) { q.k[i] = k[i]; q.s[i] = s[i]; q.p[i] = p[i]; }
-    T2V_LAUNCH(avgpool3d_k, dim3(nblocks((long)NC * Do * Ho * Wo)), dim3(256), 0, S_(st), x, x2, y, NC, D, H, W, Do, Ho, Wo, q);
-    return launch_status();
+    return pool_single(x, x2, y, NC, D, H, W, Do, Ho, Wo, k, s, p, false, st);
 }
 extern "C" int t2v_avgpool3d_bwd(const float* gy, float* gx, int NC, int D, int H, int W, int Do, int Ho, int Wo,
                                  const int32_t k[3], const int32_t s[3], const int32_t p[3], void* st) {
-    if (!gy || !gx || NC < 1 || !pool_ok(k, s, p)) return T2V_EINVAL;
-    Pool3 q;
-    for (int i = 0; i < 3; ++i) { q.k[i] = k[i]; q.s[i] = s[i]; q.p[i] = p[i]; }
-    const bool simple = p[0] == 0 && p[1] == 0 && p[2] == 0 && k[0] <= s[0] && k[1] <= s[1] && k[2] <= s[2];
-    if (simple) T2V_LAUNCH(avgpool3d_bwd_simple_k, dim3(nblocks((long)NC * D * H * W)), dim3(256), 0, S_(st), gy, gx, NC, D, H, W, Do, Ho, Wo, q);
-    else T2V_LAUNCH(avgpool3d_bwd_k, dim3(nblocks((long)NC * D * H * W)), dim3(256), 0, S_(st), gy, gx, NC, D, H, W, Do, Ho, Wo, q);
-    return launch_status();
+    return pool_single(gy, nullptr, gx, NC, D, H, W, Do, Ho, Wo, k, s, p, true, st);
 }
 
 // ---------------------------------------------------------------- row reductions (one wave per row)

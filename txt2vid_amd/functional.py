@@ -12,7 +12,7 @@ these kernels (conv fwd <-> dgrad <-> wgrad form a closed triple).
 There is ONE convolution triple, the grouped one (`ConvG` / `ConvDgradG` / `ConvDgradMaskG` / `ConvWgradG` over
 `conv_group_raw` / `conv_group_wgrad_raw`): `conv`, `relu_conv` and `linear` on a single tensor are groups of one.
 Likewise the non-local block's small ops and the spatial sum (functional_multi.py): `bmm`, `softmax_lastdim`, `max_pool2x2`,
-`sum_spatial`, `scale_add` and `add_avg_pool3d` are the grouped Functions on a list of one.
+`sum_spatial`, `scale_add`, `avg_pool3d` and `add_avg_pool3d` are the grouped Functions on a list of one.
 """
 import contextlib
 import ctypes as C
@@ -690,60 +690,14 @@ def add(a, b):
     return Add.apply(a, b)
 
 
-def _pool_args(k, s, p):
-    A = C.c_int32 * 3
-    return A(*k), A(*s), A(*p)
-
-
-def _pool_out(n, k, s, p):
-    return (n + 2 * p - k) // s + 1
-
-
-class AvgPool3d(Function):
-    """pool(x), or with `x2` pool(x + x2) in the same kernel (DownBlock: DownSample(skip) + DownSample(main) ==
-    DownSample(skip + main))."""
-
-    @staticmethod
-    def forward(ctx, x, k, s, p, x2=None):
-        x = _c(x)
-        N, Cc, D, H, W = x.shape
-        Do, Ho, Wo = _pool_out(D, k[0], s[0], p[0]), _pool_out(H, k[1], s[1], p[1]), _pool_out(W, k[2], s[2], p[2])
-        ctx.cfg = (k, s, p, (D, H, W))
-        y = torch.empty((N, Cc, Do, Ho, Wo), device=x.device, dtype=torch.float32)
-        ka, sa, pa = _pool_args(k, s, p)
-        x2 = _c(x2) if x2 is not None else None
-        check(lib().t2v_avgpool3d(_p(x), _p(x2), _p(y), N * Cc, D, H, W, Do, Ho, Wo, ka, sa, pa, _stream()), 't2v_avgpool3d')
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        k, s, p, in_sp = ctx.cfg
-        gx = AvgPool3dBwd.apply(g, k, s, p, in_sp)
-        return gx, None, None, None, (gx if ctx.needs_input_grad[4] else None)
+def _pool_out(sp, cfg):
+    """(Do, Ho, Wo) of a tensor with the spatial extents `sp` = (D, H, W) pooled under cfg = (k, s, p)."""
+    return tuple((n + 2 * p - k) // s_ + 1 for n, k, s_, p in zip(sp, *cfg))
 
 
 def add_avg_pool3d(a, b, k, s, p=(0, 0, 0)):
     """pool(a + b) in one kernel (DownBlock: DownSample(skip) + DownSample(main) == DownSample(skip + main))."""
     return avg_pool3d_group([a], [(k, s, p)], x2s=[b])[0]
-
-
-class AvgPool3dBwd(Function):
-    @staticmethod
-    def forward(ctx, g, k, s, p, in_sp):
-        g = _c(g)
-        N, Cc, Do, Ho, Wo = g.shape
-        D, H, W = in_sp
-        ctx.cfg = (k, s, p)
-        gx = torch.empty((N, Cc, D, H, W), device=g.device, dtype=torch.float32)
-        ka, sa, pa = _pool_args(k, s, p)
-        check(lib().t2v_avgpool3d_bwd(_p(g), _p(gx), N * Cc, D, H, W, Do, Ho, Wo, ka, sa, pa, _stream()),
-              't2v_avgpool3d_bwd')
-        return gx
-
-    @staticmethod
-    def backward(ctx, gg):
-        k, s, p = ctx.cfg
-        return AvgPool3d.apply(gg, k, s, p, None), None, None, None, None
 
 
 def _pool_jobs(ins, in2s, outs, cfgs, in_sps, adds=None):
@@ -752,13 +706,12 @@ def _pool_jobs(ins, in2s, outs, cfgs, in_sps, adds=None):
     arr = (PoolJob * len(ins))()
     for i, a in enumerate(arr):
         k, s_, p = cfgs[i]
-        D, H, W = in_sps[i]
         a.x, a.y = ins[i].data_ptr(), outs[i].data_ptr()
         a.x2 = in2s[i].data_ptr() if in2s is not None else None
         a.add = adds[i].data_ptr() if adds is not None else None
         a.NC = outs[i].shape[0] * outs[i].shape[1]
-        a.D, a.H, a.W = D, H, W
-        a.Do, a.Ho, a.Wo = _pool_out(D, k[0], s_[0], p[0]), _pool_out(H, k[1], s_[1], p[1]), _pool_out(W, k[2], s_[2], p[2])
+        a.D, a.H, a.W = in_sps[i]
+        a.Do, a.Ho, a.Wo = _pool_out(in_sps[i], cfgs[i])
         for j in range(3):
             a.k[j], a.s[j], a.p[j] = k[j], s_[j], p[j]
     return arr
@@ -776,11 +729,8 @@ class AvgPool3dG(Function):
         x2s = [_c(t) for t in ts[n:2 * n]] if has2 else None
         adds = [_c(t) for t in ts[(2 * n if has2 else n):]] if has_add else None
         in_sps = [tuple(x.shape[2:]) for x in xs]
-        ys = []
-        for x, (k, s_, p) in zip(xs, cfgs):
-            ys.append(torch.empty((x.shape[0], x.shape[1], _pool_out(x.shape[2], k[0], s_[0], p[0]),
-                                   _pool_out(x.shape[3], k[1], s_[1], p[1]), _pool_out(x.shape[4], k[2], s_[2], p[2])),
-                                  device=x.device, dtype=torch.float32))
+        ys = [torch.empty(tuple(x.shape[:2]) + _pool_out(sp, cfg), device=x.device, dtype=torch.float32)
+              for x, sp, cfg in zip(xs, in_sps, cfgs)]
         if adds is not None and any(a.shape != y.shape for a, y in zip(adds, ys)):
             raise ValueError('addend / pooled shape mismatch')
         check(lib().t2v_avgpool3d_multi(_pool_jobs(xs, x2s, ys, cfgs, in_sps, adds), n, _stream()), 't2v_avgpool3d_multi')
@@ -839,8 +789,8 @@ class ForkPoolG(Function):
     def forward(ctx, cfgs, *xs):
         xs = [_c(x) for x in xs]
         in_sps = [tuple(x.shape[2:]) for x in xs]
-        ys = [torch.empty((x.shape[0], x.shape[1], _pool_out(x.shape[2], k[0], s_[0], p[0]), _pool_out(x.shape[3], k[1], s_[1], p[1]),
-                           _pool_out(x.shape[4], k[2], s_[2], p[2])), device=x.device, dtype=torch.float32) for x, (k, s_, p) in zip(xs, cfgs)]
+        ys = [torch.empty(tuple(x.shape[:2]) + _pool_out(sp, cfg), device=x.device, dtype=torch.float32)
+              for x, sp, cfg in zip(xs, in_sps, cfgs)]
         check(lib().t2v_avgpool3d_multi(_pool_jobs(xs, None, ys, cfgs, in_sps), len(xs), _stream()), 't2v_avgpool3d_multi')
         ctx.cfg = (cfgs, in_sps)
         ctx.set_materialize_grads(False)
@@ -877,11 +827,10 @@ class ForkPoolG(Function):
 
 def fork_pool_group(xs, cfgs):
     """(aliases of xs, [pool_i(xs[i])]) with the aliases' gradients summed INSIDE the pooling adjoint's launch. Falls back to a
-    grouped fork + `avg_pool3d_group` for padded / overlapping windows and for tensors that need no gradient."""
+    grouped fork + `avg_pool3d_group` for tensors that need no gradient."""
     xs = list(xs)
     cfgs = tuple((tuple(k), tuple(s_), tuple(p)) for k, s_, p in cfgs)
-    plain = any(any(p) or any(kk > ss for kk, ss in zip(k, s_)) for k, s_, p in cfgs) or len(xs) > 8
-    if plain or not torch.is_grad_enabled() or not all(x.requires_grad for x in xs):
+    if not torch.is_grad_enabled() or not all(x.requires_grad for x in xs):
         xa, xb = fork_group(xs)
         return xa, avg_pool3d_group(xb, cfgs)
     res = ForkPoolG.apply(cfgs, *xs)
@@ -889,18 +838,15 @@ def fork_pool_group(xs, cfgs):
 
 
 def avg_pool3d_group(xs, cfgs, x2s=None, adds=None):
-    """cfgs[i] = (k, s, p) per tensor; x2s: pool(xs[i] + x2s[i]); adds: ... + adds[i] (pooled shape). Falls back to
-    per-tensor launches for padded / overlapping windows (their adjoint is the general gather kernel)."""
+    """cfgs[i] = (k, s, p) per tensor; x2s: pool(xs[i] + x2s[i]); adds: ... + adds[i] (pooled shape). Any window
+    the kernels take (kernel <= 4, padding >= 0), any number of tensors: one launch per 8."""
     cfgs = tuple((tuple(k), tuple(s_), tuple(p)) for k, s_, p in cfgs)
-    if any(any(p) or any(kk > ss for kk, ss in zip(k, s_)) for k, s_, p in cfgs) or len(xs) > 8:
-        ys = [AvgPool3d.apply(x, *c, x2) for x, c, x2 in zip(xs, cfgs, x2s or [None] * len(xs))]
-        return ys if adds is None else [add(y, a) for y, a in zip(ys, adds)]
     ts = list(xs) + (list(x2s) if x2s is not None else []) + (list(adds) if adds is not None else [])
     return list(AvgPool3dG.apply(cfgs, x2s is not None, adds is not None, *ts))
 
 
 def avg_pool3d(x, k, s, p=(0, 0, 0)):
-    return AvgPool3d.apply(x, tuple(k), tuple(s), tuple(p), None)
+    return avg_pool3d_group([x], [(k, s, p)])[0]
 
 
 def max_pool2x2(x):
@@ -2873,5 +2819,5 @@ def add_group(as_, bs):
     return list(AddG.apply(*(list(as_) + list(bs))))
 
 
-for _cls in (Relu, ReluMask, Add, AvgPool3d, AvgPool3dBwd, CatFeatures, SliceCols, EmbedCols, CatBatch, ConvWgradG):
+for _cls in (Relu, ReluMask, Add, CatFeatures, SliceCols, EmbedCols, CatBatch, ConvWgradG):
     _pass_none_through(_cls)
