@@ -666,6 +666,25 @@ typedef struct t2v_aug_member {
 int t2v_diffaug_fwd(const t2v_aug_member* members, int n, void* stream);
 int t2v_diffaug_bwd(const t2v_aug_member* members, int n, void* stream);
 
+/* ---- adaptive strength of that augmentation (ADA, Karras et al. 2020; opt-in, --D_aug_p / --D_ada) ------------------
+ * Gated pair: the contract of t2v_diffaug_fwd / _bwd, and clip j of member i also reads row j * row_stride of its gate block
+ * gates[i] [rows, T2V_AUG_K] (uniforms in [0, 1); columns 0, 1, 2 gate color, translation, cutout; 3-7 unused) and p[0] from
+ * DEVICE memory when the launch runs:   effective policy = policy & (1 [g0 < p] | 2 [g1 < p] | 4 [g2 < p]),  a strict fp32 <.
+ * p = 1 gives the ungated bits, an effective policy of 0 copies the clip (forward and adjoint), a clip without live color is not
+ * summed. gates[i] == NULL leaves member i ungated. Every workgroup of a split clip reads the same gate row and the same p.
+ * `gates` is a HOST array of n device pointers. T2V_EINVAL for everything the ungated pair refuses and for gates == NULL or
+ * p == NULL, before any launch.
+ * t2v_ada_update, the controller: ada float32[8] (device) = { p, sum of signs in the window, pairs in the window, D steps in the
+ * window, 0, 0, 0, 0 }. ONE workgroup adds  sum over the n levels and j < count of sgn(real[j] - fake[j])  (sgn(0) = 0) and the
+ * pair count to the window and increments the step count; when that reaches `interval` it sets
+ * p = clamp(p + sgn(ada[1] / ada[2] - target) * step, 0, 1) and zeroes ada[1..3]. All window sums are small integers (exact in
+ * fp32 in any order); the update of p is one fp32 add and two clamps. Plain stores, no atomics, no workspace. T2V_EINVAL on null
+ * pointers, n outside 1..T2V_MAX_GROUPS, count < 1, interval < 1, or a step that is negative or not finite. */
+typedef struct t2v_ada_level { const float* real; const float* fake; int32_t count; int32_t reserved; } t2v_ada_level;
+int t2v_diffaug_gated_fwd(const t2v_aug_member* members, const float* const* gates, int n, const float* p, void* stream);
+int t2v_diffaug_gated_bwd(const t2v_aug_member* members, const float* const* gates, int n, const float* p, void* stream);
+int t2v_ada_update(float* ada, const t2v_ada_level* levels, int n, float target, float step, int interval, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

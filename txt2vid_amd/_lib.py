@@ -97,6 +97,11 @@ class AugMember(C.Structure):
                 ('S', C.c_int32), ('row_stride', C.c_int32), ('rows', C.c_int32), ('policy', C.c_int32), ('reserved', C.c_int32)]
 
 
+class AdaLevel(C.Structure):
+    """t2v_ada_level (include/t2v_hip.h)."""
+    _fields_ = [('real', C.c_void_p), ('fake', C.c_void_p), ('count', C.c_int32), ('reserved', C.c_int32)]
+
+
 MAX_GROUPS = 8
 _P = C.c_void_p
 _I = C.c_int
@@ -235,6 +240,9 @@ SIGNATURES = {
     't2v_ca_bwd': [_P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
     't2v_diffaug_fwd': [_P, _I, _P],
     't2v_diffaug_bwd': [_P, _I, _P],
+    't2v_diffaug_gated_fwd': [_P, _P, _I, _P, _P],
+    't2v_diffaug_gated_bwd': [_P, _P, _I, _P, _P],
+    't2v_ada_update': [_P, _P, _I, _F, _F, _I, _P],
     't2v_prof_begin': [_I],
     't2v_prof_end': [C.POINTER(C.c_double), _I],
     't2v_version': [],

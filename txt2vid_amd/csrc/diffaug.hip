@@ -3,6 +3,17 @@
 // generated pyramid, up to T2V_MAX_GROUPS) is transformed per clip with the colour / translation / cutout map defined in
 // include/t2v_hip.h and txt2vid_amd/functional_aug.py (`aug_params`). Launch-bound work (a pyramid level has 32 K elements at
 // the benchmarked shapes): plain vector loads and stores, the clip reduction and the apply step in the same launch.
+//
+// Adaptive strength (ADA, Karras et al. 2020; opt-in through --D_aug_p / --D_ada). The GATED entry points
+// t2v_diffaug_gated_fwd / _bwd are the same kernels with one more step in front: clip j of a member also reads row j * row_stride
+// of the member's gate block g [rows, 8] (uniforms in [0, 1), drawn right behind u) and the probability p from DEVICE memory, and
+// its effective policy is  policy & (1 [g0 < p] | 2 [g1 < p] | 4 [g2 < p])  (strict fp32 <; g == p: not applied). Everything
+// behind that is the ungated code with that policy: p = 1 gives today's bits, an effective policy of 0 copies the clip (forward and
+// adjoint), a clip without live colour sums nothing. Every part of a split clip reads the same gate row and the same p. The
+// backward re-reads gates and p: p is written only by t2v_ada_update, which the trainer launches behind the D forward, never
+// between an augmentation's forward and its backward. t2v_ada_update is the controller: one workgroup adds a D step's
+// sum of sgn(u_real - u_fake) to the window kept in ada float32[8] = {p, sum, pairs, steps, 0...} and, every `interval` steps,
+// moves p by +-step towards the target and clears the window (small integers: exact in fp32 in any order).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/t2v_hip.h"
@@ -37,6 +48,11 @@ struct AugBatch {
     int begin[T2V_MAX_GROUPS + 1];      // first workgroup of member g; a member owns N * parts[g] workgroups
     int parts[T2V_MAX_GROUPS];
     int n;
+};
+
+struct AugGate {
+    const float* g[T2V_MAX_GROUPS];     // gate block of member g, or NULL: ungated
+    const float* p;                     // the probability, one float in device memory
 };
 
 struct AugP {
@@ -80,14 +96,22 @@ __device__ __forceinline__ bool aug_cut(const AugP& p, int h, int w) {
     const int parts = tb.parts[g];                                                         \
     const int local = (int)blockIdx.x - tb.begin[g];                                       \
     const int clip = local / parts, part = local - clip * parts;                           \
-    const int S = m.S, C = m.C, policy = m.policy;                                         \
+    const int S = m.S, C = m.C;                                                            \
+    int policy = m.policy;                                                                 \
+    if (GATED && tg.g[g]) {        /* uniform over the workgroup and over the parts of a clip */ \
+        const float* __restrict__ gr = tg.g[g] + (long)clip * m.row_stride * T2V_AUG_K;    \
+        const float pv = tg.p[0];                                                          \
+        policy &= (gr[0] < pv ? T2V_AUG_COLOR : 0) | (gr[1] < pv ? T2V_AUG_TRANSLATION : 0) | (gr[2] < pv ? T2V_AUG_CUTOUT : 0); \
+    }                                                                                      \
     const int V = m.T * S * S;                 /* voxels of one channel */                 \
     const int n = C * V;                       /* elements of the clip  */                 \
     const AugP p = aug_params(m.u + (long)clip * m.row_stride * T2V_AUG_K, S, policy);     \
     const int per = (V + parts - 1) / parts;                                               \
     const int v0 = part * per, v1 = min(V, v0 + per)
 
-__global__ __launch_bounds__(256) void diffaug_fwd_k(AugBatch tb) {
+// (an effective policy of 0 falls through the same code: no sum, no shift, no box — a copy)
+template <bool GATED>
+__global__ __launch_bounds__(256) void diffaug_fwd_k(AugBatch tb, AugGate tg) {
     __shared__ float red[4];
     AUG_LOCATE();
     const float* __restrict__ x = m.x + (long)clip * n;
@@ -132,7 +156,8 @@ __global__ __launch_bounds__(256) void diffaug_fwd_k(AugBatch tb) {
 }
 
 // dL/dx from dL/dy (m.x -> m.y). gcol = the gradient masked by the cutout and shifted back; then the colour map's adjoint.
-__global__ __launch_bounds__(256) void diffaug_bwd_k(AugBatch tb) {
+template <bool GATED>
+__global__ __launch_bounds__(256) void diffaug_bwd_k(AugBatch tb, AugGate tg) {
     __shared__ float red[4];
     AUG_LOCATE();
     const float* __restrict__ gy = m.x + (long)clip * n;
@@ -205,7 +230,7 @@ extern "C" int t2v_diffaug_fwd(const t2v_aug_member* members, int n, void* st) {
     long blocks = 0;
     const int rc = aug_batch(tb, members, n, &blocks);
     if (rc != T2V_OK) return rc;
-    T2V_LAUNCH(diffaug_fwd_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
+    T2V_LAUNCH(diffaug_fwd_k<false>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, AugGate{});
     return launch_status();
 }
 
@@ -214,6 +239,85 @@ extern "C" int t2v_diffaug_bwd(const t2v_aug_member* members, int n, void* st) {
     long blocks = 0;
     const int rc = aug_batch(tb, members, n, &blocks);
     if (rc != T2V_OK) return rc;
-    T2V_LAUNCH(diffaug_bwd_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb);
+    T2V_LAUNCH(diffaug_bwd_k<false>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, AugGate{});
+    return launch_status();
+}
+
+static int aug_gate(AugGate& tg, const float* const* gates, int n, const float* p) {
+    if (!gates || !p) return T2V_EINVAL;
+    for (int g = 0; g < T2V_MAX_GROUPS; ++g) tg.g[g] = g < n ? gates[g] : nullptr;
+    tg.p = p;
+    return T2V_OK;
+}
+
+extern "C" int t2v_diffaug_gated_fwd(const t2v_aug_member* members, const float* const* gates, int n, const float* p, void* st) {
+    AugBatch tb;
+    AugGate tg;
+    long blocks = 0;
+    int rc = aug_batch(tb, members, n, &blocks);
+    if (rc == T2V_OK) rc = aug_gate(tg, gates, n, p);
+    if (rc != T2V_OK) return rc;
+    T2V_LAUNCH(diffaug_fwd_k<true>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, tg);
+    return launch_status();
+}
+
+extern "C" int t2v_diffaug_gated_bwd(const t2v_aug_member* members, const float* const* gates, int n, const float* p, void* st) {
+    AugBatch tb;
+    AugGate tg;
+    long blocks = 0;
+    int rc = aug_batch(tb, members, n, &blocks);
+    if (rc == T2V_OK) rc = aug_gate(tg, gates, n, p);
+    if (rc != T2V_OK) return rc;
+    T2V_LAUNCH(diffaug_bwd_k<true>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, tg);
+    return launch_status();
+}
+
+// ---- the controller of p ---------------------------------------------------------------------------------------------------
+struct AdaBatch {
+    t2v_ada_level l[T2V_MAX_GROUPS];
+    int n;
+};
+
+// One workgroup. Every term is -1, 0 or +1 and there are at most a few thousand of them: the sums are exact in any order.
+__global__ __launch_bounds__(256) void ada_update_k(float* __restrict__ ada, AdaBatch tb, float pairs, float target, float step,
+                                                    float interval) {
+    __shared__ float red[4];
+    float acc = 0.f;
+    for (int g = 0; g < tb.n; ++g) {
+        const float* __restrict__ r = tb.l[g].real;
+        const float* __restrict__ f = tb.l[g].fake;
+        for (int j = threadIdx.x; j < tb.l[g].count; j += 256) {
+            const float a = r[j], b = f[j];
+            acc += (a > b ? 1.f : 0.f) - (a < b ? 1.f : 0.f);             // sgn(a - b), 0 for a tie (and for a NaN)
+        }
+    }
+    const float sum = block_sum(acc, red);
+    if (threadIdx.x != 0) return;
+    float p = ada[0], s = ada[1] + sum, c = ada[2] + pairs, k = ada[3] + 1.f;
+    if (k >= interval) {
+        const float rt = s / c;                                           // c >= 1
+        const float dir = (rt > target ? 1.f : 0.f) - (rt < target ? 1.f : 0.f);
+        p = p + dir * step;                                               // dir * step is exact: one rounding, in the add
+        p = p < 0.f ? 0.f : p;
+        p = p > 1.f ? 1.f : p;
+        s = c = k = 0.f;
+    }
+    ada[0] = p; ada[1] = s; ada[2] = c; ada[3] = k;
+}
+
+extern "C" int t2v_ada_update(float* ada, const t2v_ada_level* levels, int n, float target, float step, int interval, void* st) {
+    if (!ada || !levels || n < 1 || n > T2V_MAX_GROUPS || interval < 1) return T2V_EINVAL;
+    if (!(step >= 0.f) || !(step <= 3.0e38f)) return T2V_EINVAL;          // negative, NaN or infinite
+    AdaBatch tb;
+    long pairs = 0;
+    for (int g = 0; g < T2V_MAX_GROUPS; ++g) {
+        tb.l[g] = g < n ? levels[g] : t2v_ada_level{};
+        if (g >= n) continue;
+        if (!levels[g].real || !levels[g].fake || levels[g].count < 1) return T2V_EINVAL;
+        pairs += levels[g].count;
+    }
+    if (pairs > (1L << 24)) return T2V_EINVAL;                            // the window stays exact in fp32
+    tb.n = n;
+    T2V_LAUNCH(ada_update_k, dim3(1), dim3(256), 0, S_(st), ada, tb, (float)pairs, target, step, (float)interval);
     return launch_status();
 }

@@ -40,9 +40,13 @@ class HostDraws(object):
         """eps ~ N(0, 1) [b, d] of the generator's conditioning augmentation (one draw per generator forward, like z)."""
         return torch.randn(b, d).to(device, non_blocking=True)
 
-    def aug(self, b, device):
-        """One block u [b, AUG_K] of uniforms for an augmentation of D's inputs (functional_aug), drawn when it is consumed."""
-        return torch.rand(b, AUG_K).to(device, non_blocking=True)
+    def aug(self, b, device, gated=False):
+        """One block u [b, AUG_K] of uniforms for an augmentation of D's inputs (functional_aug), drawn when it is consumed.
+        `gated` (adaptive strength): (u, g), the gate block g [b, AUG_K] drawn immediately after u."""
+        u = torch.rand(b, AUG_K).to(device, non_blocking=True)
+        if not gated:
+            return u
+        return u, torch.rand(b, AUG_K).to(device, non_blocking=True)
 
     def perm(self, n, device):
         """A non-identity permutation of range(n) from numpy's global RNG (util/misc.gen_perm), as a device int32 tensor."""
@@ -61,11 +65,14 @@ class StaticDraws(object):
         self.ca_dim = ca_dim                        # conditioning augmentation: one eps [batch, ca_dim] per G forward (0: none)
         self.n_levels, self.n_gen, self.gp, self.sub = n_levels, n_gen_phases, gp, subsample_input
         # augmentation of D's inputs (--D_aug): blocks [batch, AUG_K] per iteration, in the eager order of consumption — a real and
-        # a generated block per D step and at G part 0, a generated block per later G step (0: none, today's layout)
-        if n_aug not in (0, 2 * n_d_steps + n_g_steps + 1):
-            raise ValueError('an iteration of %d D and %d G steps consumes %d augmentation blocks, not %d'
+        # a generated block per D step and at G part 0, a generated block per later G step (0: none, today's layout). With gated
+        # augmentation (adaptive strength) twice as many: every parameter block is followed by its gate block
+        if n_aug not in (0, 2 * n_d_steps + n_g_steps + 1, 2 * (2 * n_d_steps + n_g_steps + 1)):
+            raise ValueError('an iteration of %d D and %d G steps consumes %d augmentation blocks (twice as many with gates), not %d'
                              % (n_d_steps, n_g_steps, 2 * n_d_steps + n_g_steps + 1, n_aug))
         self.n_aug = n_aug
+        self.gated = n_aug > 2 * n_d_steps + n_g_steps + 1
+        self._w = 2 if self.gated else 1            # blocks per draw: u alone, or u and its gate block g right behind it
         self.bs = [batch]
         for _ in range(n_levels - 1):
             self.bs.append((self.bs[-1] + 1) // 2)
@@ -111,7 +118,8 @@ class StaticDraws(object):
         stream. With conditioning augmentation every G forward draws its eps first, in front of its phases: z, eps 0, phases 0,
         alphas, then eps j, phases j for each later forward j. With augmentation of D's inputs every D step draws a real and a
         generated block in front of its alphas, G part 0 draws a real and a generated block behind the last D step, and every later
-        G forward j draws a generated block behind its phases."""
+        G forward j draws a generated block behind its phases. With gated augmentation every one of these blocks u is followed at
+        once by its gate block g (u, g, u, g, ...), next to it in the staging buffer."""
         slot = self._slot
         self._slot = (slot + 1) % self.RING
         if self.h_events[slot] is not None:
@@ -132,25 +140,26 @@ class StaticDraws(object):
         off = blk = 0
         for _ in range(self.n_d_steps):
             if self.n_aug:
-                self.h_u[blk].copy_(torch.rand(self.batch, AUG_K))
-                self.h_u[blk + 1].copy_(torch.rand(self.batch, AUG_K))
-                blk += 2
+                for _ in range(2 * self._w):
+                    self.h_u[blk].copy_(torch.rand(self.batch, AUG_K))
+                    blk += 1
             if self.gp:
                 for b in self.bs:
                     self.h_a[off:off + b] = torch.rand(b, 1, 1, 1, 1).reshape(b)
                     off += b
         if self.n_aug:
-            self.h_u[blk].copy_(torch.rand(self.batch, AUG_K))
-            self.h_u[blk + 1].copy_(torch.rand(self.batch, AUG_K))
-            blk += 2
+            for _ in range(2 * self._w):
+                self.h_u[blk].copy_(torch.rand(self.batch, AUG_K))
+                blk += 1
         for j in range(1, self.n_g_steps):
             if self.ca_dim:
                 self.h_eps[j].copy_(torch.randn(self.batch, self.ca_dim))
             for k in range(self.n_gen * j, self.n_gen * (j + 1)):
                 self.h_int[self.n_levels + k] = int(torch.randint(2, (1,)))
             if self.n_aug:
-                self.h_u[blk].copy_(torch.rand(self.batch, AUG_K))
-                blk += 1
+                for _ in range(self._w):
+                    self.h_u[blk].copy_(torch.rand(self.batch, AUG_K))
+                    blk += 1
         if self.n_perms:
             from .util.misc import gen_perm
             for k in range(self.n_perms):
@@ -198,11 +207,11 @@ class StaticDraws(object):
         self._e += 1
         return self.d_eps[k]
 
-    def aug(self, b, device):
-        assert b == self.batch and self._u < self.n_aug
+    def aug(self, b, device, gated=False):
+        assert b == self.batch and self._u < self.n_aug and bool(gated) == self.gated
         k = self._u
-        self._u += 1
-        return self.d_u[k]
+        self._u += self._w
+        return (self.d_u[k], self.d_u[k + 1]) if self.gated else self.d_u[k]
 
     def rewind(self):
         self._i = self._a = self._p = self._e = self._u = 0

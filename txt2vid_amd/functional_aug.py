@@ -26,6 +26,34 @@ The map is affine per clip. Adjoint: mask and shift the incoming gradient back, 
 saturation s g + (1 - s) mean_channels(g); brightness is the identity. The backward is ONCE differentiable: the gradient
 penalty's interpolates are formed from the already augmented clips and stay leaves, so no second-order adjoint is needed.
 fp32 whatever the convolution precision.
+
+ADAPTIVE STRENGTH (ADA, Karras et al. 2020; opt-in through `--D_aug_p` / `--D_ada`; kernels `t2v_diffaug_gated_fwd` /
+`_bwd`, controller `t2v_ada_update` behind gan/ada.py). THE DEFINITION, stated once:
+
+  Gating. Every parameter block u [B, 8] gets a GATE block g [B, 8] of uniforms in [0, 1), drawn immediately after u from the
+  same generator. Columns 0, 1, 2 gate color, translation, cutout; columns 3-7 are unused. Clip j of a member reads gate row
+  j * row_stride, the rule its parameter row follows, so a clip gets the same gates at every pyramid level. The effective policy
+  of a clip is   policy & (1 [g0 < p] | 2 [g1 < p] | 4 [g2 < p])   with a strict fp32 < (g == p: not applied) and p read from
+  DEVICE memory by the launch; the rest of the transformation is unchanged. So p = 1 is the ungated transformation bit for bit,
+  p = 0 is a copy, a clip whose effective policy is 0 is copied in the forward and in the adjoint, and a clip without live color
+  needs no clip sum. Wherever a parameter block is reused its gate block is reused with it.
+
+  Statistic. r_t = mean over pyramid levels l and pairs j < b_l of sgn(u_r[l][j] - u_f[l][j]), sgn(0) = 0, over the
+  unconditional real and generated logits that enter the `lu` term of the D loss of the FIRST discriminator (the paired form: the
+  default loss, RSGAN, is relativistic and its logits have no anchored zero, so the paper's E[sign(D(real))] means nothing here).
+
+  Controller. Device state ada float32[8] = {p, sum of sgn in the window, pairs in the window, D steps in the window, 0, 0, 0, 0}.
+  Per D step, behind that step's D forward, ONE launch adds the step's sign sum and pair count and increments ada[3]; when
+  ada[3] >= interval it sets p <- clamp(p + sgn(ada[1] / ada[2] - target) * step, 0, 1) and zeroes ada[1..3].
+  step = B * interval / (1000 * kclips), computed on the host in double and passed as one fp32. The window sums are small
+  integers (exact in fp32 in any order) and the update is one fp32 add and two clamps, so a numpy float32 restatement agrees
+  with the device bitwise. Order within D step j: augment with the current p, D forward, observe / update; the next augmentation
+  launch in stream order (the G step's too) sees the new p.
+
+  THE p-INVARIANT. The backward re-reads the gates and p instead of keeping a snapshot. p is written by the observe launch
+  alone, which sits behind the D forward: inside a D step the augmentation's forward and (if any) backward both precede it in
+  stream order or carry no gradient at all (the D step's clips are detached), and a G step has no write between its forward and
+  its backward. Forward and backward of one augmentation therefore see one value of p.
 """
 import torch
 from torch.autograd import Function
@@ -83,12 +111,19 @@ def _members(srcs, dsts, us, strides, policy):
     return arr
 
 
+def _gate_ptrs(gates):
+    import ctypes
+    return (ctypes.c_void_p * len(gates))(*[None if g is None else g.data_ptr() for g in gates])
+
+
 class DiffAug(Function):
     """ys = T(xs): ONE forward launch for all members; ONE backward launch over the members that require a gradient (none: no
-    launch). The parameter blocks carry no gradient (host draws)."""
+    launch). The parameter blocks carry no gradient (host draws). `gate`: None, or (gates, p) — one gate block (or None: that
+    member is ungated) per tensor and the device float p; then both launches are the gated ones and the backward re-reads gates
+    and p (p is not snapshotted: see THE p-INVARIANT in the module docstring)."""
 
     @staticmethod
-    def forward(ctx, policy, us, strides, *xs):
+    def forward(ctx, policy, us, strides, gate, *xs):
         if not 1 <= len(xs) <= MAX_GROUPS:
             raise ValueError('1 to %d tensors per augmentation launch, got %d' % (MAX_GROUPS, len(xs)))
         if len(us) != len(xs) or len(strides) != len(xs):
@@ -100,34 +135,62 @@ class DiffAug(Function):
                 raise ValueError('augmentation takes clips [N, C, T, S, S] with square frames, got %s' % (tuple(x.shape),))
             if u.dim() != 2 or u.shape[1] != K:
                 raise ValueError('an augmentation block is [B, %d], got %s' % (K, tuple(u.shape)))
+        if gate is not None:
+            gates, p = gate
+            if len(gates) != len(xs):
+                raise ValueError('one gate block (or None) per tensor')
+            gates = [None if g is None else _c(g) for g in gates]
+            for g, u in zip(gates, us):
+                if g is not None and g.shape != u.shape:
+                    raise ValueError('a gate block has the shape of its parameter block %s, got %s' % (tuple(u.shape), tuple(g.shape)))
+            p = _c(p)
+            if p.numel() < 1:
+                raise ValueError('p is one float in device memory')
+            gate = (gates, p)
         ys = [torch.empty_like(x) for x in xs]
-        check(lib().t2v_diffaug_fwd(_members(xs, ys, us, strides, policy), len(xs), _stream()), 't2v_diffaug_fwd')
+        if gate is None:
+            check(lib().t2v_diffaug_fwd(_members(xs, ys, us, strides, policy), len(xs), _stream()), 't2v_diffaug_fwd')
+        else:
+            check(lib().t2v_diffaug_gated_fwd(_members(xs, ys, us, strides, policy), _gate_ptrs(gate[0]), len(xs), gate[1].data_ptr(),
+                                              _stream()), 't2v_diffaug_gated_fwd')
         ctx.set_materialize_grads(False)
         ctx.cfg = (policy, tuple(strides))
         ctx.us = us                                    # (plain tensors that never require grad: no saved-tensor hooks needed)
-        ctx.mark_non_differentiable(*[y for y, need in zip(ys, ctx.needs_input_grad[3:]) if not need])
+        ctx.gate = gate
+        ctx.mark_non_differentiable(*[y for y, need in zip(ys, ctx.needs_input_grad[4:]) if not need])
         return tuple(ys)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *gys):
         policy, strides = ctx.cfg
-        live = [i for i, g in enumerate(gys) if g is not None and ctx.needs_input_grad[3 + i]]
+        live = [i for i, g in enumerate(gys) if g is not None and ctx.needs_input_grad[4 + i]]
         gxs = [None] * len(gys)
         if live:
             gs = [_c(gys[i]) for i in live]
             outs = [torch.empty_like(g) for g in gs]
-            check(lib().t2v_diffaug_bwd(_members(gs, outs, [ctx.us[i] for i in live], [strides[i] for i in live], policy),
-                                        len(live), _stream()), 't2v_diffaug_bwd')
+            ms = _members(gs, outs, [ctx.us[i] for i in live], [strides[i] for i in live], policy)
+            if ctx.gate is None:
+                check(lib().t2v_diffaug_bwd(ms, len(live), _stream()), 't2v_diffaug_bwd')
+            else:
+                # the same gates and the SAME p the forward saw: nothing writes p between the two (THE p-INVARIANT)
+                gates, p = ctx.gate
+                check(lib().t2v_diffaug_gated_bwd(ms, _gate_ptrs([gates[i] for i in live]), len(live), p.data_ptr(), _stream()),
+                      't2v_diffaug_gated_bwd')
             for i, o in zip(live, outs):
                 gxs[i] = o
-        return (None, None, None) + tuple(gxs)
+        return (None, None, None, None) + tuple(gxs)
 
 
-def diffaug(xs, us, strides, policy):
+def diffaug(xs, us, strides, policy, gates=None, p=None):
     """Augment the clips `xs` (a list of [N, C, T, S, S] device tensors) in one launch; member i reads row j * strides[i] of its
-    block us[i] [B, K] for its clip j. `policy`: bits or a comma-separated string. Returns the list of augmented clips."""
+    block us[i] [B, K] for its clip j. `policy`: bits or a comma-separated string. Returns the list of augmented clips.
+    `gates` (a list of gate blocks [B, K], None entries for ungated members) and `p` (a device float32 tensor, read when the
+    launch runs) come together: each transformation is then applied per clip with probability p (see ADAPTIVE STRENGTH above)."""
     bits = parse_policy(policy) if isinstance(policy, str) else int(policy)
     if not bits:
         return list(xs)
-    return list(DiffAug.apply(bits, tuple(us), tuple(strides), *xs))
+    if (gates is None) != (p is None):
+        raise ValueError('gates and p come together')
+    gate = None if gates is None else (tuple(gates), p)
+    return list(DiffAug.apply(bits, tuple(us), tuple(strides), gate, *xs))

@@ -38,6 +38,13 @@ class CondGan(object):
         self.gp_scale = gp_scale          # data-parallel: world_size, else 1
         self.gen_ema = gen_ema            # gan.ema.GenAverage of `gen` (--G_ema, not in the reference), or None
         self.discrim_sn = None            # gan.spectral.SpectralNorm of `discrims` (--D_sn, not in the reference), or None
+        self.ada = None                   # gan.ada.AdaState, the controller of the augmentation's p (--D_ada, not in the reference), or None
+
+    def _observe(self, discrim, u_r, u_f):
+        """--D_ada: the unconditional logits of the `lu` term of a D step feed the controller (the first discriminator's alone):
+        one launch behind this D forward."""
+        if self.ada is not None and discrim is self.discrims[0]:
+            self.ada.observe(list(u_r), list(u_f))
 
     def _discrim_weighted_sum(self, losses, kl=None, kl_coeff=0.0):
         """cond_gan.py:26-31: mean over discriminators, or lambda-weighted sum. `kl`: the generator's conditioning-augmentation
@@ -68,6 +75,7 @@ class CondGan(object):
                     discrim(x=real, cond=fake_cond, xbar=None)
                 fake_cc = discrim(x=fake, cond=real_cond, xbar=None)
                 lu = TF.scalar_mean([loss(fake=f[0], real=r[0]) for f, r in zip(fake_cc, real_cc)])
+                self._observe(discrim, [r[0] for r in real_cc], [f[0] for f in fake_cc])
                 l1 = TF.scalar_mean([loss(fake=f[1], real=r[1]) for f, r in zip(fake_cc, real_cc)])
                 l2 = TF.scalar_mean([loss(fake=f[1], real=r[1]) for f, r in zip(real_ic, real_cc)])
                 # (lu + (l1 + l2)/2) / 2
@@ -79,6 +87,7 @@ class CondGan(object):
                 fake_pred = [f[0] for f in discrim(x=fake, cond=None, xbar=None)]
             if loss is not None and fake_pred is not None and real_pred is not None:
                 l = TF.scalar_mean([loss(fake=f, real=r) for f, r in zip(fake_pred, real_pred)])
+                self._observe(discrim, real_pred, fake_pred)
         if l is not None and gp_lambda > 0:
             gp = gradient_penalty(discrim, real_x=real, fake_x=fake, real_cond=real_cond, fake_cond=fake_cond,
                                   scale=self.gp_scale)
@@ -117,6 +126,7 @@ class CondGan(object):
         both, gp_res = res[:n], res[n:]
         b = [r.size(0) for r in real]
         u_r, u_f = TF.split_rows_group([o[0] for o in both], b)
+        self._observe(discrim, u_r, u_f)
         if cond:
             c_r, c_f = TF.split_rows_group([o[1] for o in both], b)
             # D(real, mismatched captions): second head on the real half's trunk features
@@ -272,6 +282,8 @@ class CondGan(object):
         if self.discrim_sn is not None:
             # the discriminators' own `weight` entries hold W / sigma; the master weights and the power-iteration vectors go here
             res['discrim_sn'] = self.discrim_sn.state_dict()
+        if self.ada is not None:
+            res['ada'] = self.ada.state_dict()
         return res
 
     def load_from_dict(self, to_load):
@@ -287,6 +299,10 @@ class CondGan(object):
             # a file without the key (written without --G_ema, or by the reference) leaves the average a copy of the loaded `gen`;
             # a file with the key loaded into a run without an average ignores it
             self.gen_ema.load_state_dict(to_load.get('gen_ema'), to_load.get('gen_ema_updates', 0))
+        if self.ada is not None:
+            # a file without the key (written without --D_ada, or by the reference) starts from p0 with an empty window; a file with
+            # the key loaded into a run without a controller ignores it
+            self.ada.load_state_dict(to_load.get('ada'))
 
 
 def _can_batch(real, fake):

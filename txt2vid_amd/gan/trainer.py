@@ -8,7 +8,8 @@ gen_perm (numpy), 4x GP alpha (losses.py:140-145), gen_perm for real_pred (train
 --discrim_steps N / --gen_steps M schedule (trainer.py:228-263): gen_perm + 4x alpha once per D step, then
 gen_perm for real_pred, then 3x Subsample per later G forward (DESIGN "D:G step schedule"). With --D_aug every D step
 draws a real and a generated augmentation block in front of its alphas, G part 0 a real and a generated block, every later G
-step a generated block behind its forward's draws.
+step a generated block behind its forward's draws. With gated augmentation (--D_aug_p < 1 or --D_ada) every such
+block is followed at once by its gate block.
 """
 import argparse
 import os
@@ -39,9 +40,32 @@ def _aug_policy(text):
     return text
 
 
+def _probability(text):
+    v = float(text)
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError('--D_aug_p takes a probability in [0, 1], got %r' % text)
+    return v
+
+
+def _ada_target(text):
+    v = float(text)
+    if not 0.0 < v < 1.0:
+        raise argparse.ArgumentTypeError('--D_ada takes a target in (0, 1) (the paper uses 0.6), got %r' % text)
+    return v
+
+
+def _positive(kind, flag):
+    def parse(text):
+        v = kind(text)
+        if not v > 0:
+            raise argparse.ArgumentTypeError('%s must be positive, got %r' % (flag, text))
+        return v
+    return parse
+
+
 def add_params_to_parser(parser):
     """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema,
-    --G_ema_start, --D_aug and --D_sn are new."""
+    --G_ema_start, --D_aug, --D_aug_p, --D_ada, --D_ada_interval, --D_ada_kclips and --D_sn are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
     parser.add_argument('--log_period', type=int, default=20)
@@ -68,6 +92,20 @@ def add_params_to_parser(parser):
     parser.add_argument('--D_aug', type=_aug_policy, default='',
                         help='(new) differentiable augmentation of every clip the discriminator sees: a comma-separated subset of '
                              'color,translation,cutout (applied in that order); empty = off')
+    parser.add_argument('--D_aug_p', type=_probability, default=None,
+                        help='(new) apply each transformation of --D_aug per clip with this probability, in [0, 1]: the fixed '
+                             'strength, or the initial one under --D_ada. Default 1.0 without --D_ada (every clip, as --D_aug '
+                             'alone), 0.0 with it')
+    parser.add_argument('--D_ada', type=_ada_target, default=None, metavar='TARGET',
+                        help='(new) adaptive strength (ADA, Karras et al. 2020): steer the probability of --D_aug during training so '
+                             'that the mean sign of D(real) - D(generated) over paired logits stays at TARGET, 0 < TARGET < 1 '
+                             '(the paper uses 0.6). Single-GPU runs only. 0.6 and the defaults of the two flags below are the '
+                             "paper's values for images: nobody has tuned them for video or for the paired statistic")
+    parser.add_argument('--D_ada_interval', type=_positive(int, '--D_ada_interval'), default=4,
+                        help="(new) discriminator steps per update of the probability (the paper's value for images; untuned here)")
+    parser.add_argument('--D_ada_kclips', type=_positive(float, '--D_ada_kclips'), default=500.0,
+                        help='(new) thousands of clips in which the probability can move from 0 to 1 '
+                             "(the paper's value for images; untuned here)")
     parser.add_argument('--D_sn', action='store_true', default=False,
                         help='(new) spectral normalisation of every Conv3d / Linear weight of the discriminators: one power '
                              'iteration after each discriminator update')
@@ -142,6 +180,21 @@ class TrainStep(object):
         from ..functional_aug import parse_policy
         self.aug = parse_policy(getattr(params, 'D_aug', ''))
         self._xs_g = None                 # the augmented real pyramid of G part 0 (reused by later fused G steps)
+        # adaptive strength (--D_aug_p / --D_ada): each transformation applied per clip with probability p, read from
+        # device memory by the gated launches. p is the controller's (gan.ada, updated behind every D forward) or a fixed value;
+        # --D_aug_p 1.0 without a controller is the ungated path: no gate draws, the old entry points
+        from .ada import check_args
+        check_args(params)
+        self.ada = getattr(gan, 'ada', None) if self.aug else None
+        if getattr(gan, 'ada', None) is not None and not self.aug:
+            raise ValueError('a controller of the augmentation strength (gan.ada) needs a non-empty --D_aug')
+        if self.ada is not None and grad_sync is not None:
+            raise ValueError('--D_ada in a data-parallel run: synchronising the window across ranks is not implemented')
+        p_fixed = getattr(params, 'D_aug_p', None)
+        self.gated = bool(self.aug) and (self.ada is not None or (p_fixed is not None and p_fixed != 1.0))
+        self._p = None
+        if self.gated:
+            self._p = self.ada.p if self.ada is not None else _fixed_p(p_fixed, device)
         self._fused = False
         self._one = None                  # dL/dL = 1 for both backward passes: one persistent 0-d tensor (no fill launch per pass)
         # the store_false quirk of --no_mean_*_loss (trainer.py:236-237,260-261): the loss of every step is divided by the step
@@ -194,20 +247,25 @@ class TrainStep(object):
 
     def _augment(self, real, fake):
         """(real, fake) through the augmentation, both lists (either may be None) in one launch: a block of draws for the real
-        clips first, then one for the generated clips. Under --subsample_input level l's sample j reads base row j * 2^l."""
+        clips first, then one for the generated clips. Under --subsample_input level l's sample j reads base row j * 2^l. Gated:
+        every block comes with its gate block, and the launch reads the current p."""
         if not self.aug:
             return real, fake
         from ..functional_aug import diffaug
-        xs, us, strides = [], [], []
+        xs, us, gs, strides = [], [], [], []
         for clips in (real, fake):
             if clips is None:
                 continue
-            u = TF.draws.aug(self._batch, self.device)
+            if self.gated:
+                u, g = TF.draws.aug(self._batch, self.device, gated=True)         # the gate block right behind its parameter block
+            else:
+                u, g = TF.draws.aug(self._batch, self.device), None
             for l, t in enumerate(clips):
                 xs.append(t)
                 us.append(u)
+                gs.append(g)
                 strides.append(2 ** l if self.params.subsample_input else 1)
-        out = diffaug(xs, us, strides, self.aug)
+        out = diffaug(xs, us, strides, self.aug, gs, self._p) if self.gated else diffaug(xs, us, strides, self.aug)
         n = len(real) if real is not None else 0
         return (out[:n] if real is not None else None), (out[n:] if fake is not None else None)
 
@@ -333,6 +391,17 @@ class TrainStep(object):
         return self.lD, self.lG, self.fake, self.xs
 
 
+_FIXED_P = {}
+
+
+def _fixed_p(p, device):
+    """A fixed probability as one float in device memory (made once per value and device, by copy: no fill launch per step)."""
+    key = (str(torch.device(device)), float(p))
+    if key not in _FIXED_P:
+        _FIXED_P[key] = torch.tensor([float(p)], dtype=torch.float32).to(device)
+    return _FIXED_P[key]
+
+
 def train_iteration(gan, x, cond, optD, optG, losses, params, device, end2end=False, z=None, grad_sync=None):
     """One eager pass of the loop body. x: [B,C,T,H,W] device tensor. Returns (lossD, lossG, fake, xs);
     the losses are 0-d device tensors (no host sync here)."""
@@ -359,7 +428,7 @@ class GraphedTrainStep(object):
                                     gp=params.gp_lambda > 0, subsample_input=params.subsample_input,
                                     n_perms=(N + 1) * len(gan.discrims) if cond_dim else 0, n_d_steps=N, n_g_steps=M,
                                     ca_dim=getattr(gan.gen, 'ca_dim', 0) if cond_dim else 0,
-                                    n_aug=2 * N + M + 1 if self.ts.aug else 0)
+                                    n_aug=(2 * N + M + 1) * (2 if self.ts.gated else 1) if self.ts.aug else 0)
         self.x = torch.empty(batch_shape, device=device, dtype=torch.float32)
         # conditional path: the sentence code is computed outside the graphs (its sequence length varies) into a fixed buffer
         self.cond = torch.empty((batch_shape[0], cond_dim), device=device, dtype=torch.float32) if cond_dim else None
@@ -585,6 +654,7 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
     gen_loss = RollingAvg(window_size=params.loss_window_size)
     discrim_loss = RollingAvg(window_size=params.loss_window_size)
     kl_loss = RollingAvg(window_size=params.loss_window_size) if getattr(gan.gen, 'ca_dim', 0) else None     # conditioning augmentation
+    ada, ada_p = getattr(gan, 'ada', None), None             # --D_ada: p is read with the losses and printed at the log period
     avg_iter = RollingAvg(window_size=max(1, params.log_period))
     avg_load = RollingAvg(window_size=max(1, params.log_period))
     load_watch, iter_watch = Stopwatch(), Stopwatch()
@@ -638,19 +708,23 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 # copies). The rolling averages lag by one iteration.
                 lKL = graphed.ts.lKL
                 if loss_ring is None:
-                    loss_ring = [(torch.empty(3, device=lD.device), torch.empty(3).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+                    loss_ring = [(torch.empty(4, device=lD.device), torch.zeros(4).pin_memory(), torch.cuda.Event()) for _ in range(2)]
                 dbuf, hbuf, ev = loss_ring[iteration & 1]
                 if _X_BY_MEMCPY:
                     TF.copy_into(lD.reshape(1), dbuf[0:1])
                     TF.copy_into(lG.reshape(1), dbuf[1:2])
                     if lKL is not None:
                         TF.copy_into(lKL.reshape(1), dbuf[2:3])
+                    if ada is not None:
+                        TF.copy_into(ada.p, dbuf[3:4])
                     hbuf.copy_(dbuf, non_blocking=True)
                 else:                                    # copy kernels writing the pinned buffer in place: no copy-engine hop behind the graph
                     TF._copy2d(lD.reshape(1), 0, 1, hbuf, 0, 1, 1, 1)
                     TF._copy2d(lG.reshape(1), 0, 1, hbuf, 1, 1, 1, 1)
                     if lKL is not None:
                         TF._copy2d(lKL.reshape(1), 0, 1, hbuf, 2, 1, 1, 1)
+                    if ada is not None:
+                        TF._copy2d(ada.p, 0, 1, hbuf, 3, 1, 1, 1)     # (travels with the losses: no sync of its own)
                 ev.record()
                 if pending is not None:
                     pending[1].synchronize()
@@ -658,6 +732,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                     gen_loss.update(float(pending[0][1]))
                     if kl_loss is not None:
                         kl_loss.update(float(pending[0][2]))
+                    if ada is not None:
+                        ada_p = float(pending[0][3])
                 pending = (hbuf, ev)
             else:
                 ts = TrainStep(gan, optD, optG, losses, params, device, end2end, grad_sync)       # (= train_iteration)
@@ -666,6 +742,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 gen_loss.update(float(lG))
                 if kl_loss is not None:
                     kl_loss.update(float(ts.lKL))
+                if ada is not None and params.log_period > 0 and iteration % params.log_period == 0:
+                    ada_p = float(ada.p)
             # checkpoint: the reference tests `save_example_period` here (trainer.py:269) and never reads
             # --save_model_period; the intended flag is used (SURVEY §8a defect 3).
             if writer and ((iteration == 1 and params.save_initial) or (params.save_model_period > 0 and
@@ -685,6 +763,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 if kl_loss is not None:
                     status('Iter %d, KL (conditioning augmentation, inside Loss_G with weight %g): %.4f' %
                            (iteration, gan.gen.ca_kl_coeff, kl_loss.get()))
+                if ada_p is not None:
+                    status('Iter %d, augmentation probability p (--D_ada, target %g): %.4f' % (iteration, ada.target, ada_p))
                 torch.cuda.reset_peak_memory_stats()
             if writer and params.save_example_period > 0 and ((iteration == 1 and params.save_initial_examples) or
                                                               iteration % params.save_example_period == 0):

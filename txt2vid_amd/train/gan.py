@@ -36,6 +36,9 @@ def _model(spec, args, kind='D', **kw):
 def main(args):
     from ..gan.spectral import check_flags, check_checkpoint
     check_flags(args)
+    from ..gan.ada import check_args, AdaState
+    # --D_aug_p / --D_ada: the rules are checked before a process group forms (a data-parallel start with --D_ada is refused)
+    check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
     from .. import dist as tdist
     rank, world = tdist.init_from_env('nccl')
     from ..util.misc import limit_host_threads
@@ -93,6 +96,12 @@ def main(args):
     resumed_rng, resumed_iter, resumed_ema, resumed_sn = None, 0, None, None
     gan = CondGan(gen=gen, discrims=discrims, cond_encoder=txt_encoder, discrim_names=args.D_names,
                   discrim_lambdas=args.D_lambdas, gp_scale=float(world))
+    if args.D_ada is not None:
+        # adaptive strength of --D_aug (not in the reference): the controller's state lives on the device and in the checkpoint
+        # (key 'ada'); a file without the key starts from --D_aug_p
+        gan.ada = AdaState(args.D_ada, args.D_ada_interval, args.D_ada_kclips, args.D_aug_p, device)
+        status('Adaptive augmentation strength: target %g, update every %d D steps, %g kclips, initial p %g (defaults are the '
+               "paper's values for images, untuned for video)" % (args.D_ada, args.D_ada_interval, args.D_ada_kclips, args.D_aug_p))
     if args.weights is not None:
         to_load = torch.load(args.weights, map_location=device, weights_only=False)
         resumed_sn = check_checkpoint(to_load, args.D_sn, args.weights)
@@ -105,6 +114,9 @@ def main(args):
         if 'gen_ema' in to_load and args.G_ema > 0:
             resumed_ema = (to_load['gen_ema'], to_load.get('gen_ema_updates', 0))
         del to_load
+    if gan.ada is not None:
+        st = gan.ada.ada.tolist()
+        status('Augmentation probability p = %r; window: sign sum %g over %g pairs in %g D steps' % (st[0], st[1], st[2], st[3]))
     if world > 1:
         # replicas bit-identical before the first step (whatever each rank's init / checkpoint read produced), then per-rank
         # generators for everything drawn per iteration (z, sub-sample phases, GP alphas, caption permutations)
