@@ -440,6 +440,24 @@ int t2v_adam_multi(const t2v_adam_job* jobs, int njobs, float lr, float b1, floa
    momentum buffer (may be NULL when momentum == 0), .v unused; first_step: buf = g (torch's first-step rule). */
 int t2v_sgd_multi(const t2v_adam_job* jobs, int njobs, float lr, float momentum, float gscale, int first_step, void* stream);
 int t2v_adam_tick(float* state, float b1, float b2, void* stream);
+/* ---- learning-rate schedule inside the replayed graph (--lr_decay; not in the reference) ----
+ * Schedule state, float32[2] in device memory per optimiser: { k = updates made so far, factor of the current update }.
+ * t2v_lr_tick (one thread) computes, in double, the factor of update k — of training iteration it = k / spi (integer division;
+ * spi = optimiser updates per iteration) —
+ *     frac = (it - start) / (end - start);   factor = 1 if frac <= 0,  fin if frac >= 1,  else
+ *     T2V_LR_LINEAR: 1 - (1 - fin) * frac        T2V_LR_COSINE: fin + (1 - fin) * 0.5 * (1 + cos(pi * frac))
+ * stores it rounded to float in state[1] and then sets state[0] = k + 1. T2V_EINVAL, before any launch, on state == NULL, an
+ * unknown kind, start < 0, end <= start, fin outside [0, 1] or spi < 1.
+ * The _sched forms are t2v_adam_multi / t2v_sgd_multi with the rate  lr * lr_scale[1]  (ONE float multiply, formed before
+ * everything else): lr_scale is a schedule state, read at run time. Same kernels otherwise (one body, instantiated twice), same
+ * refusals, and T2V_EINVAL on lr_scale == NULL. Called with the float product as lr, the unscheduled forms give the same bits. */
+#define T2V_LR_LINEAR 1
+#define T2V_LR_COSINE 2
+int t2v_lr_tick(float* state, int kind, int64_t start, int64_t end, double fin, int spi, void* stream);
+int t2v_adam_multi_sched(const t2v_adam_job* jobs, int njobs, float lr, const float* lr_scale, float b1, float b2, float eps,
+                         float bc1, float bc2, float gscale, const float* step_dev, void* stream);
+int t2v_sgd_multi_sched(const t2v_adam_job* jobs, int njobs, float lr, const float* lr_scale, float momentum, float gscale,
+                        int first_step, void* stream);
 
 /* ---- weight average (opt-in EMA of the generator; not in the reference) ------------- */
 /* Multi-tensor like t2v_adam_multi: `jobs` is a HOST array of (average, parameter, element count) with device pointers

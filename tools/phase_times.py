@@ -13,7 +13,7 @@ import sys
 d = sys.argv[1]
 ms_step = float(sys.argv[2])
 f = glob.glob(d + '/*/*_kernel_trace.csv')[0]
-rows = [(int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'].split('(')[0][:70]) for r in csv.DictReader(open(f))]
+rows = [(int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'].split('(')[0].split('<')[0].split()[-1][:70]) for r in csv.DictReader(open(f))]   # ('void adam_multi_k<>(...)' -> 'adam_multi_k')
 rows.sort()
 # densest window of 8 steps (the replays), as tools/gap_analysis.py
 t0, t1 = rows[0][0], rows[-1][1]

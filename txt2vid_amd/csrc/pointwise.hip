@@ -2304,9 +2304,16 @@ struct AdamBatch {
     float* p[ADAM_MT]; const float* g[ADAM_MT]; float* m[ADAM_MT]; float* v[ADAM_MT];
     int n[ADAM_MT]; int begin[ADAM_MT + 1]; int njobs;
 };
+// The kernel exists once and is instantiated twice. adam_multi_k<> is t2v_adam_multi's kernel as it always was: the same parameter
+// list, the same instructions. adam_multi_k<const float*> (t2v_adam_multi_sched) takes one more argument, a schedule
+// state {k, factor} in device memory, and first scales the rate by the factor read at run time: ONE separate float multiply in
+// front of the unchanged lr / bc1, so the result equals the unscheduled kernel called with the float product, bit for bit.
+__device__ __forceinline__ float lr_factor(const float* sched) { return sched[1]; }
+template <typename... Sched>
 __global__ __launch_bounds__(256) void adam_multi_k(AdamBatch tb, float lr, float b1, float b2, float eps, float bc1, float bc2,
-                                                     float gscale, const float* step_dev) {
+                                                     float gscale, const float* step_dev, Sched... sched) {
     if (step_dev) { bc1 = step_dev[1]; bc2 = step_dev[2]; }
+    if constexpr (sizeof...(Sched) > 0) lr = lr * lr_factor(sched...);
     const float step = lr / bc1;
     const float isq = 1.f / sqrtf(bc2);
     int lo = 0, hi = tb.njobs;                         // largest j with begin[j] <= blockIdx.x
@@ -2342,8 +2349,9 @@ __global__ __launch_bounds__(256) void adam_multi_k(AdamBatch tb, float lr, floa
         p[i] = p[i] - step * (mi / (sqrtf(vi) * isq + eps));
     }
 }
-extern "C" int t2v_adam_multi(const t2v_adam_job* jobs, int njobs, float lr, float b1, float b2, float eps, float bc1, float bc2,
-                              float gscale, const float* step_dev, void* st) {
+// lr_scale == NULL: t2v_adam_multi (the old kernel, the old arguments); else t2v_adam_multi_sched
+static int adam_multi(const t2v_adam_job* jobs, int njobs, float lr, float b1, float b2, float eps, float bc1, float bc2,
+                      float gscale, const float* step_dev, const float* lr_scale, void* st) {
     if (!jobs || njobs < 1) return T2V_EINVAL;
     for (int i = 0; i < njobs; ++i)
         if (!jobs[i].p || !jobs[i].g || !jobs[i].m || !jobs[i].v || jobs[i].n < 1 || jobs[i].n > 0x7fffffffL) return T2V_EINVAL;
@@ -2361,13 +2369,29 @@ extern "C" int t2v_adam_multi(const t2v_adam_job* jobs, int njobs, float lr, flo
         tb.begin[ADAM_MT] = (int)blocks;
         tb.njobs = cnt;
         if (blocks > 0x7fffffffL) return T2V_EINVAL;
-        T2V_LAUNCH(adam_multi_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, b1, b2, eps, bc1, bc2, gscale, step_dev);
+        if (lr_scale)
+            T2V_LAUNCH(adam_multi_k<const float*>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, b1, b2, eps, bc1, bc2, gscale,
+                       step_dev, lr_scale);
+        else
+            T2V_LAUNCH(adam_multi_k<>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, b1, b2, eps, bc1, bc2, gscale, step_dev);
     }
     return launch_status();
 }
+extern "C" int t2v_adam_multi(const t2v_adam_job* jobs, int njobs, float lr, float b1, float b2, float eps, float bc1, float bc2,
+                              float gscale, const float* step_dev, void* st) {
+    return adam_multi(jobs, njobs, lr, b1, b2, eps, bc1, bc2, gscale, step_dev, nullptr, st);
+}
+extern "C" int t2v_adam_multi_sched(const t2v_adam_job* jobs, int njobs, float lr, const float* lr_scale, float b1, float b2, float eps,
+                                    float bc1, float bc2, float gscale, const float* step_dev, void* st) {
+    if (!lr_scale) return T2V_EINVAL;
+    return adam_multi(jobs, njobs, lr, b1, b2, eps, bc1, bc2, gscale, step_dev, lr_scale, st);
+}
 // torch.optim.SGD(lr, momentum) semantics (the reference's --sgd branch, train/gan.py:86-89), multi-tensor like adam_multi_k:
 // buf = first ? g : momentum * buf + g ;  p -= lr * (momentum != 0 ? buf : g).   jobs[i].m = momentum buffer, .v unused
-__global__ __launch_bounds__(256) void sgd_multi_k(AdamBatch tb, float lr, float momentum, float gscale, int first) {
+// (one kernel, two instances, like adam_multi_k: sgd_multi_k<const float*> scales lr by the factor in a float multiply of its own)
+template <typename... Sched>
+__global__ __launch_bounds__(256) void sgd_multi_k(AdamBatch tb, float lr, float momentum, float gscale, int first, Sched... sched) {
+    if constexpr (sizeof...(Sched) > 0) lr = lr * lr_factor(sched...);
     int lo = 0, hi = tb.njobs;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tb.begin[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
     const int j = lo;
@@ -2383,7 +2407,8 @@ __global__ __launch_bounds__(256) void sgd_multi_k(AdamBatch tb, float lr, float
         p[i] = p[i] - lr * d;
     }
 }
-extern "C" int t2v_sgd_multi(const t2v_adam_job* jobs, int njobs, float lr, float momentum, float gscale, int first_step, void* st) {
+static int sgd_multi(const t2v_adam_job* jobs, int njobs, float lr, float momentum, float gscale, int first_step, const float* lr_scale,
+                     void* st) {
     if (!jobs || njobs < 1) return T2V_EINVAL;
     for (int i = 0; i < njobs; ++i)
         if (!jobs[i].p || !jobs[i].g || (momentum != 0.f && !jobs[i].m) || jobs[i].n < 1 || jobs[i].n > 0x7fffffffL) return T2V_EINVAL;
@@ -2402,9 +2427,20 @@ extern "C" int t2v_sgd_multi(const t2v_adam_job* jobs, int njobs, float lr, floa
         tb.begin[ADAM_MT] = (int)blocks;
         tb.njobs = cnt;
         if (blocks > 0x7fffffffL) return T2V_EINVAL;
-        T2V_LAUNCH(sgd_multi_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, momentum, gscale, first_step);
+        if (lr_scale)
+            T2V_LAUNCH(sgd_multi_k<const float*>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, momentum, gscale, first_step, lr_scale);
+        else
+            T2V_LAUNCH(sgd_multi_k<>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, momentum, gscale, first_step);
     }
     return launch_status();
+}
+extern "C" int t2v_sgd_multi(const t2v_adam_job* jobs, int njobs, float lr, float momentum, float gscale, int first_step, void* st) {
+    return sgd_multi(jobs, njobs, lr, momentum, gscale, first_step, nullptr, st);
+}
+extern "C" int t2v_sgd_multi_sched(const t2v_adam_job* jobs, int njobs, float lr, const float* lr_scale, float momentum, float gscale,
+                                   int first_step, void* st) {
+    if (!lr_scale) return T2V_EINVAL;
+    return sgd_multi(jobs, njobs, lr, momentum, gscale, first_step, lr_scale, st);
 }
 // step state {step, bc1, bc2}: step += 1 and the bias corrections 1 - beta^step, evaluated in double and
 // rounded to float exactly like the host path does (python float -> c_float).
@@ -2419,6 +2455,29 @@ __global__ void adam_tick_k(float* state, float b1, float b2) {
 extern "C" int t2v_adam_tick(float* state, float b1, float b2, void* st) {
     if (!state) return T2V_EINVAL;
     T2V_LAUNCH(adam_tick_k, dim3(1), dim3(64), 0, S_(st), state, b1, b2);
+    return launch_status();
+}
+// learning-rate schedule state {k, factor}: the factor of update k, i.e. of training iteration it = k / spi, in double
+// and rounded to float; then k += 1. Both ends are branches, so the factor is exactly 1 up to `start` and exactly `fin` from
+// `end` on. One thread, the adam_tick_k pattern; k is a float like Adam's step (exact up to 2^24 updates).
+__global__ void lr_tick_k(float* state, int kind, double start, double end, double fin, int spi) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const float k = state[0];
+        const double it = (double)((long)k / (long)spi);
+        const double frac = (it - start) / (end - start);
+        double f;
+        if (!(frac > 0.0)) f = 1.0;
+        else if (frac >= 1.0) f = fin;
+        else if (kind == T2V_LR_LINEAR) f = 1.0 - (1.0 - fin) * frac;
+        else f = fin + (1.0 - fin) * 0.5 * (1.0 + cos(3.14159265358979323846 * frac));
+        state[1] = (float)f;
+        state[0] = k + 1.f;
+    }
+}
+extern "C" int t2v_lr_tick(float* state, int kind, int64_t start, int64_t end, double fin, int spi, void* st) {
+    if (!state || (kind != T2V_LR_LINEAR && kind != T2V_LR_COSINE) || start < 0 || end <= start || !(fin >= 0.0 && fin <= 1.0) || spi < 1)
+        return T2V_EINVAL;
+    T2V_LAUNCH(lr_tick_k, dim3(1), dim3(64), 0, S_(st), state, kind, (double)start, (double)end, fin, spi);
     return launch_status();
 }
 

@@ -65,7 +65,8 @@ def _positive(kind, flag):
 
 def add_params_to_parser(parser):
     """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema,
-    --G_ema_start, --D_aug, --D_aug_p, --D_ada, --D_ada_interval, --D_ada_kclips and --D_sn are new."""
+    --G_ema_start, --D_aug, --D_aug_p, --D_ada, --D_ada_interval, --D_ada_kclips, --D_sn, --lr_decay, --lr_decay_iters,
+    --lr_decay_start and --lr_final are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
     parser.add_argument('--log_period', type=int, default=20)
@@ -109,6 +110,17 @@ def add_params_to_parser(parser):
     parser.add_argument('--D_sn', action='store_true', default=False,
                         help='(new) spectral normalisation of every Conv3d / Linear weight of the discriminators: one power '
                              'iteration after each discriminator update')
+    parser.add_argument('--lr_decay', choices=('none', 'linear', 'cosine'), default='none',
+                        help='(new) decay --G_lr and --D_lr by one factor per training iteration, inside the replayed graph: '
+                             'linear or cosine from 1 at --lr_decay_start to --lr_final at --lr_decay_iters. '
+                             '--lr_decay linear --lr_decay_iters 100000 is the TGANv2 recipe')
+    parser.add_argument('--lr_decay_iters', type=int, default=None, metavar='T',
+                        help='(new) the training iteration at which the decay ends (required with --lr_decay); the rate stays at '
+                             'its final value from there on')
+    parser.add_argument('--lr_decay_start', type=int, default=None, metavar='S',
+                        help='(new) iterations at the full rate before the decay begins (default 0)')
+    parser.add_argument('--lr_final', type=float, default=None, metavar='F',
+                        help='(new) the fraction of the base rate that remains at the end, in [0, 1] (default 0)')
     return parser
 
 
@@ -195,6 +207,12 @@ class TrainStep(object):
         self._p = None
         if self.gated:
             self._p = self.ada.p if self.ada is not None else _fixed_p(p_fixed, device)
+        # learning-rate decay (--lr_decay): the optimisers tick and read device-resident schedule states themselves; the
+        # only thing to hold here is that the states count this schedule's steps per iteration
+        for opt, n, flag in ((optD, self.n_d, '--discrim_steps'), (optG, self.n_g, '--gen_steps')):
+            sch = getattr(opt, 'lr_sched', None)
+            if sch is not None and sch.spi != n:
+                raise ValueError('the learning-rate schedule counts %d optimiser steps per iteration, %s is %d' % (sch.spi, flag, n))
         self._fused = False
         self._one = None                  # dL/dL = 1 for both backward passes: one persistent 0-d tensor (no fill launch per pass)
         # the store_false quirk of --no_mean_*_loss (trainer.py:236-237,260-261): the loss of every step is divided by the step
@@ -655,6 +673,10 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
     discrim_loss = RollingAvg(window_size=params.loss_window_size)
     kl_loss = RollingAvg(window_size=params.loss_window_size) if getattr(gan.gen, 'ca_dim', 0) else None     # conditioning augmentation
     ada, ada_p = getattr(gan, 'ada', None), None             # --D_ada: p is read with the losses and printed at the log period
+    # --lr_decay: the rates printed at the log period come from the host mirror of the formula, counted on from the schedule
+    # iteration the device state stood at when training started (read once, here)
+    lr_sched = getattr(getattr(optD, 'lr_sched', None), 'sched', None)
+    lr_it0 = lr_sched.counters()['D'] // lr_sched.spi['D'] if lr_sched is not None else 0
     avg_iter = RollingAvg(window_size=max(1, params.log_period))
     avg_load = RollingAvg(window_size=max(1, params.log_period))
     load_watch, iter_watch = Stopwatch(), Stopwatch()
@@ -752,6 +774,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 # extra keys next to the reference's layout (its loader ignores them; its files, which lack them, still load here)
                 to_save = {'optG': optG.state_dict(), 'optD': optD.state_dict(), 'iteration': iteration, 'rng_state': get_rng_state()}
                 to_save.update(gan.save_dict())
+                if lr_sched is not None:
+                    to_save['lr_sched'] = lr_sched.state_dict()
                 torch.save(to_save, '%s/iter_%d_lossG_%.4f_lossD_%.4f' % (params.out, iteration, gen_loss.get(),
                                                                           discrim_loss.get()))
             if params.log_period > 0 and iteration % params.log_period == 0:
@@ -765,6 +789,11 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                            (iteration, gan.gen.ca_kl_coeff, kl_loss.get()))
                 if ada_p is not None:
                     status('Iter %d, augmentation probability p (--D_ada, target %g): %.4f' % (iteration, ada.target, ada_p))
+                if lr_sched is not None:
+                    it = lr_it0 + iteration - 1
+                    f = lr_sched.factor(it)
+                    status('Iter %d, learning rates (--lr_decay %s, iteration %d of the schedule, factor %.6g): D %.6g G %.6g' % (
+                        iteration, lr_sched.kind, it + 1, f, optD.param_groups[0]['lr'] * f, optG.param_groups[0]['lr'] * f))
                 torch.cuda.reset_peak_memory_stats()
             if writer and params.save_example_period > 0 and ((iteration == 1 and params.save_initial_examples) or
                                                               iteration % params.save_example_period == 0):

@@ -50,6 +50,7 @@ class Adam(torch.optim.Optimizer):
         self.grad_scale = 1.0
         self.step_dev = None          # device-resident step counter (set by `make_capturable`)
         self.weight_hook = None       # gan.spectral.SpectralNorm of this optimiser's weights (--D_sn), or None
+        self.lr_sched = None          # gan.lr_sched.OptSchedule: this optimiser's side of --lr_decay, or None
 
     def make_capturable(self, device):
         """Keep the step number on the device so that a captured HIP graph applies the right bias
@@ -91,6 +92,9 @@ class Adam(torch.optim.Optimizer):
         if self.step_dev is not None:
             b1, b2 = self.param_groups[0]['betas']
             TF.check(TF.lib().t2v_adam_tick(TF._p(self.step_dev), b1, b2, TF._stream()), 't2v_adam_tick')
+        sched = getattr(self, 'lr_sched', None)
+        if sched is not None:
+            sched.tick()                      # --lr_decay: this update's factor into device memory, eager and captured alike
         touched = []
         for group in self.param_groups:
             b1, b2 = group['betas']
@@ -121,7 +125,8 @@ class Adam(torch.optim.Optimizer):
                     by_step.setdefault(st['step'], []).append((p, g, st['exp_avg'], st['exp_avg_sq']))
                 touched.append(p)
             for step, items in by_step.items():
-                TF.adam_step_multi(items, group['lr'], b1, b2, group['eps'], step, self.grad_scale, self.step_dev)
+                TF.adam_step_multi(items, group['lr'], b1, b2, group['eps'], step, self.grad_scale, self.step_dev,
+                                   None if sched is None else sched.state)
         if self.weight_hook is not None:
             # spectral norm: the parameters hold W / sigma again before they are re-packed — EVERY normalised weight does, also one
             # that had no gradient in this step (u, v and sigma moved on), so all of them join the re-pack
@@ -141,6 +146,7 @@ class SGD(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=0, nesterov=False))
         self.grad_scale = 1.0
         self.weight_hook = None       # as in Adam
+        self.lr_sched = None          # as in Adam
 
     def make_capturable(self, device):
         """Nothing step-dependent lives on the host once the momentum buffers exist (they do after the eager warm-up)."""
@@ -155,6 +161,9 @@ class SGD(torch.optim.Optimizer):
         TF.grad_sink_flush()
         if self.weight_hook is not None:
             self.weight_hook.project_grads()
+        sched = getattr(self, 'lr_sched', None)
+        if sched is not None:
+            sched.tick()
         touched = []
         for group in self.param_groups:
             mu = float(group['momentum'])
@@ -179,6 +188,10 @@ class SGD(torch.optim.Optimizer):
                 arr = (AdamJob * len(items))()
                 for a, (p, g, m) in zip(arr, items):
                     a.p, a.g, a.m, a.v, a.n = p.data_ptr(), g.data_ptr(), (m.data_ptr() if m is not None else None), None, p.numel()
+                if sched is not None:
+                    TF.check(TF.lib().t2v_sgd_multi_sched(arr, len(items), group['lr'], TF._p(sched.state), mu, self.grad_scale,
+                                                          is_first, TF._stream()), 't2v_sgd_multi_sched')
+                    continue
                 TF.check(TF.lib().t2v_sgd_multi(arr, len(items), group['lr'], mu, self.grad_scale, is_first, TF._stream()),
                          't2v_sgd_multi')
         if self.weight_hook is not None:

@@ -39,6 +39,8 @@ def main(args):
     from ..gan.ada import check_args, AdaState
     # --D_aug_p / --D_ada: the rules are checked before a process group forms (a data-parallel start with --D_ada is refused)
     check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
+    from ..gan import lr_sched
+    lr_sched.check_args(args)            # --lr_decay: likewise refused here, before a process group forms
     from .. import dist as tdist
     rank, world = tdist.init_from_env('nccl')
     from ..util.misc import limit_host_threads
@@ -93,7 +95,7 @@ def main(args):
     else:
         optD = Adam(D_params, lr=args.D_lr, betas=(args.D_beta1, args.D_beta2))
         optG = Adam(G_params, lr=args.G_lr, betas=(args.G_beta1, args.G_beta2))
-    resumed_rng, resumed_iter, resumed_ema, resumed_sn = None, 0, None, None
+    resumed_rng, resumed_iter, resumed_ema, resumed_sn, resumed_lr = None, 0, None, None, None
     gan = CondGan(gen=gen, discrims=discrims, cond_encoder=txt_encoder, discrim_names=args.D_names,
                   discrim_lambdas=args.D_lambdas, gp_scale=float(world))
     if args.D_ada is not None:
@@ -113,10 +115,23 @@ def main(args):
         resumed_rng, resumed_iter = to_load.get('rng_state'), int(to_load.get('iteration', 0))
         if 'gen_ema' in to_load and args.G_ema > 0:
             resumed_ema = (to_load['gen_ema'], to_load.get('gen_ema_updates', 0))
+        resumed_lr = to_load.get('lr_sched')
         del to_load
     if gan.ada is not None:
         st = gan.ada.ada.tolist()
         status('Augmentation probability p = %r; window: sign sum %g over %g pairs in %g D steps' % (st[0], st[1], st[2], st[3]))
+    if args.lr_decay != 'none':
+        # learning-rate decay inside the replayed graph (not in the reference): two floats of device state per optimiser, saved
+        # under the checkpoint's key 'lr_sched'. Every rank ticks identical state, so data-parallel runs need no exchange
+        sched = lr_sched.LrSchedule(args.lr_decay, args.lr_decay_iters, args.lr_decay_start, args.lr_final, args.discrim_steps,
+                                    args.gen_steps, device).attach(optD, optG)
+        for note in sched.load_state_dict(resumed_lr, resumed_iter):
+            status('Learning-rate schedule: ' + note)
+        k = sched.counters()
+        status('Learning-rate schedule: %s from iteration %d to %d, final fraction %g; D at update %d, G at update %d' % (
+            args.lr_decay, args.lr_decay_start, args.lr_decay_iters, args.lr_final, k['D'], k['G']))
+    elif resumed_lr is not None:
+        status('the checkpoint holds a learning-rate schedule state (%s); without --lr_decay it is ignored' % (resumed_lr,))
     if world > 1:
         # replicas bit-identical before the first step (whatever each rank's init / checkpoint read produced), then per-rank
         # generators for everything drawn per iteration (z, sub-sample phases, GP alphas, caption permutations)
