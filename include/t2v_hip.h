@@ -458,6 +458,26 @@ int t2v_adam_multi_sched(const t2v_adam_job* jobs, int njobs, float lr, const fl
                          float bc1, float bc2, float gscale, const float* step_dev, void* stream);
 int t2v_sgd_multi_sched(const t2v_adam_job* jobs, int njobs, float lr, const float* lr_scale, float momentum, float gscale,
                         int first_step, void* stream);
+/* ---- gradient guard inside the replayed graph (--grad_guard / --D_clip / --G_clip; not in the reference) ----
+ * Guard state, float32[8] in device memory per optimiser:
+ *     { coef, skip, norm, steps, skipped, clipped, 0, 0 }
+ * t2v_grad_sumsq_multi takes the job array of the update launches (reads .g and .n only), batched like t2v_adam_multi: block b
+ * of the call writes sum((g * gscale)^2) over its 4096-element chunk to partials[b], b counted over the whole call, with a plain
+ * store in a fixed summation order (no atomics). `partials` must hold sum(ceil(n / 4096)) floats.
+ * t2v_grad_guard (one block) adds partials[0 .. nchunks) in a fixed order in double, norm = (float)sqrt(sum), and writes
+ *     skip = norm is inf or NaN;  coef = skip or clip <= 0 ? 1 : min(1, clip / (norm + 1e-6f))  (exactly 1.0f when not below 1);
+ *     steps += 1;  skipped += skip;  clipped += (coef < 1).
+ * The _guard forms are t2v_adam_multi(_sched) / t2v_sgd_multi(_sched) / t2v_adam_tick reading that state at run time
+ * (lr_scale may be NULL: no schedule): with skip != 0 they return without a store (the tick does not advance), otherwise they
+ * use gscale * coef (ONE float multiply) for gscale. Called with the float product as gscale, the unguarded forms give the same
+ * bits. T2V_EINVAL, before any launch, on a NULL pointer, njobs < 1, n < 1, nchunks < 1 or a NaN clip. */
+int t2v_grad_sumsq_multi(const t2v_adam_job* jobs, int njobs, float gscale, float* partials, void* stream);
+int t2v_grad_guard(const float* partials, int nchunks, float clip, float* state, void* stream);
+int t2v_adam_multi_guard(const t2v_adam_job* jobs, int njobs, float lr, const float* lr_scale, float b1, float b2, float eps,
+                         float bc1, float bc2, float gscale, const float* step_dev, const float* guard, void* stream);
+int t2v_sgd_multi_guard(const t2v_adam_job* jobs, int njobs, float lr, const float* lr_scale, float momentum, float gscale,
+                        int first_step, const float* guard, void* stream);
+int t2v_adam_tick_guard(float* state, float b1, float b2, const float* guard, void* stream);
 
 /* ---- weight average (opt-in EMA of the generator; not in the reference) ------------- */
 /* Multi-tensor like t2v_adam_multi: `jobs` is a HOST array of (average, parameter, element count) with device pointers

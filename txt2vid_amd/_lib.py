@@ -208,6 +208,11 @@ SIGNATURES = {
     't2v_lr_tick': [_P, _I, _L, _L, C.c_double, _I, _P],
     't2v_adam_multi_sched': [_P, _I, _F, _P, _F, _F, _F, _F, _F, _F, _P, _P],
     't2v_sgd_multi_sched': [_P, _I, _F, _P, _F, _F, _I, _P],
+    't2v_grad_sumsq_multi': [_P, _I, _F, _P, _P],
+    't2v_grad_guard': [_P, _I, _F, _P, _P],
+    't2v_adam_multi_guard': [_P, _I, _F, _P, _F, _F, _F, _F, _F, _F, _P, _P, _P],
+    't2v_sgd_multi_guard': [_P, _I, _F, _P, _F, _F, _I, _P, _P],
+    't2v_adam_tick_guard': [_P, _F, _F, _P, _P],
     't2v_ema_multi': [_P, _I, _F, _F, _P, _F, _P],
     't2v_ema_tick': [_P, _P],
     't2v_swap_multi': [_P, _I, _P],

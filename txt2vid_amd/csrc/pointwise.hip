@@ -2308,12 +2308,30 @@ struct AdamBatch {
 // list, the same instructions. adam_multi_k<const float*> (t2v_adam_multi_sched) takes one more argument, a schedule
 // state {k, factor} in device memory, and first scales the rate by the factor read at run time: ONE separate float multiply in
 // front of the unchanged lr / bc1, so the result equals the unscheduled kernel called with the float product, bit for bit.
+// The guarded instances (t2v_adam_multi_guard) come about the same way: a trailing GuardArg wraps the float32[8] guard
+// state {coef, skip, ...} that t2v_grad_guard wrote in front of this launch. A guarded kernel returns before its first store when
+// skip != 0 and otherwise replaces gscale by gscale * coef, again ONE float multiply of its own: the guarded launch equals the
+// unguarded one called with the float product. The pack is (schedule state)? (GuardArg)?; the two old instances are untouched.
+struct GuardArg { const float* s; };
+template <typename... X> struct pack_has_guard { static constexpr bool value = false; };
+template <typename H, typename... X> struct pack_has_guard<H, X...> { static constexpr bool value = pack_has_guard<X...>::value; };
+template <typename... X> struct pack_has_guard<GuardArg, X...> { static constexpr bool value = true; };
+template <typename... X> struct pack_has_sched { static constexpr bool value = false; };
+template <typename... X> struct pack_has_sched<const float*, X...> { static constexpr bool value = true; };
 __device__ __forceinline__ float lr_factor(const float* sched) { return sched[1]; }
+__device__ __forceinline__ float lr_factor(const float* sched, GuardArg) { return sched[1]; }
+__device__ __forceinline__ const float* guard_of(GuardArg g) { return g.s; }
+__device__ __forceinline__ const float* guard_of(const float*, GuardArg g) { return g.s; }
 template <typename... Sched>
 __global__ __launch_bounds__(256) void adam_multi_k(AdamBatch tb, float lr, float b1, float b2, float eps, float bc1, float bc2,
                                                      float gscale, const float* step_dev, Sched... sched) {
+    if constexpr (pack_has_guard<Sched...>::value) {
+        const float* gd = guard_of(sched...);
+        if (gd[1] != 0.f) return;                      // a non-finite norm: this step is skipped, nothing is stored
+        gscale = gscale * gd[0];
+    }
     if (step_dev) { bc1 = step_dev[1]; bc2 = step_dev[2]; }
-    if constexpr (sizeof...(Sched) > 0) lr = lr * lr_factor(sched...);
+    if constexpr (pack_has_sched<Sched...>::value) lr = lr * lr_factor(sched...);
     const float step = lr / bc1;
     const float isq = 1.f / sqrtf(bc2);
     int lo = 0, hi = tb.njobs;                         // largest j with begin[j] <= blockIdx.x
@@ -2349,9 +2367,10 @@ __global__ __launch_bounds__(256) void adam_multi_k(AdamBatch tb, float lr, floa
         p[i] = p[i] - step * (mi / (sqrtf(vi) * isq + eps));
     }
 }
-// lr_scale == NULL: t2v_adam_multi (the old kernel, the old arguments); else t2v_adam_multi_sched
+// lr_scale == NULL: t2v_adam_multi (the old kernel, the old arguments); else t2v_adam_multi_sched. guard != NULL: the guarded
+// instances, with or without the schedule state
 static int adam_multi(const t2v_adam_job* jobs, int njobs, float lr, float b1, float b2, float eps, float bc1, float bc2,
-                      float gscale, const float* step_dev, const float* lr_scale, void* st) {
+                      float gscale, const float* step_dev, const float* lr_scale, void* st, const float* guard = nullptr) {
     if (!jobs || njobs < 1) return T2V_EINVAL;
     for (int i = 0; i < njobs; ++i)
         if (!jobs[i].p || !jobs[i].g || !jobs[i].m || !jobs[i].v || jobs[i].n < 1 || jobs[i].n > 0x7fffffffL) return T2V_EINVAL;
@@ -2369,7 +2388,13 @@ static int adam_multi(const t2v_adam_job* jobs, int njobs, float lr, float b1, f
         tb.begin[ADAM_MT] = (int)blocks;
         tb.njobs = cnt;
         if (blocks > 0x7fffffffL) return T2V_EINVAL;
-        if (lr_scale)
+        if (guard && lr_scale)
+            T2V_LAUNCH((adam_multi_k<const float*, GuardArg>), dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, b1, b2, eps, bc1, bc2,
+                       gscale, step_dev, lr_scale, GuardArg{guard});
+        else if (guard)
+            T2V_LAUNCH(adam_multi_k<GuardArg>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, b1, b2, eps, bc1, bc2, gscale,
+                       step_dev, GuardArg{guard});
+        else if (lr_scale)
             T2V_LAUNCH(adam_multi_k<const float*>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, b1, b2, eps, bc1, bc2, gscale,
                        step_dev, lr_scale);
         else
@@ -2386,12 +2411,22 @@ extern "C" int t2v_adam_multi_sched(const t2v_adam_job* jobs, int njobs, float l
     if (!lr_scale) return T2V_EINVAL;
     return adam_multi(jobs, njobs, lr, b1, b2, eps, bc1, bc2, gscale, step_dev, lr_scale, st);
 }
+extern "C" int t2v_adam_multi_guard(const t2v_adam_job* jobs, int njobs, float lr, const float* lr_scale, float b1, float b2, float eps,
+                                    float bc1, float bc2, float gscale, const float* step_dev, const float* guard, void* st) {
+    if (!guard) return T2V_EINVAL;
+    return adam_multi(jobs, njobs, lr, b1, b2, eps, bc1, bc2, gscale, step_dev, lr_scale, st, guard);
+}
 // torch.optim.SGD(lr, momentum) semantics (the reference's --sgd branch, train/gan.py:86-89), multi-tensor like adam_multi_k:
 // buf = first ? g : momentum * buf + g ;  p -= lr * (momentum != 0 ? buf : g).   jobs[i].m = momentum buffer, .v unused
 // (one kernel, two instances, like adam_multi_k: sgd_multi_k<const float*> scales lr by the factor in a float multiply of its own)
 template <typename... Sched>
 __global__ __launch_bounds__(256) void sgd_multi_k(AdamBatch tb, float lr, float momentum, float gscale, int first, Sched... sched) {
-    if constexpr (sizeof...(Sched) > 0) lr = lr * lr_factor(sched...);
+    if constexpr (pack_has_guard<Sched...>::value) {
+        const float* gd = guard_of(sched...);
+        if (gd[1] != 0.f) return;
+        gscale = gscale * gd[0];
+    }
+    if constexpr (pack_has_sched<Sched...>::value) lr = lr * lr_factor(sched...);
     int lo = 0, hi = tb.njobs;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tb.begin[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
     const int j = lo;
@@ -2408,7 +2443,7 @@ __global__ __launch_bounds__(256) void sgd_multi_k(AdamBatch tb, float lr, float
     }
 }
 static int sgd_multi(const t2v_adam_job* jobs, int njobs, float lr, float momentum, float gscale, int first_step, const float* lr_scale,
-                     void* st) {
+                     void* st, const float* guard = nullptr) {
     if (!jobs || njobs < 1) return T2V_EINVAL;
     for (int i = 0; i < njobs; ++i)
         if (!jobs[i].p || !jobs[i].g || (momentum != 0.f && !jobs[i].m) || jobs[i].n < 1 || jobs[i].n > 0x7fffffffL) return T2V_EINVAL;
@@ -2427,7 +2462,12 @@ static int sgd_multi(const t2v_adam_job* jobs, int njobs, float lr, float moment
         tb.begin[ADAM_MT] = (int)blocks;
         tb.njobs = cnt;
         if (blocks > 0x7fffffffL) return T2V_EINVAL;
-        if (lr_scale)
+        if (guard && lr_scale)
+            T2V_LAUNCH((sgd_multi_k<const float*, GuardArg>), dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, momentum, gscale, first_step,
+                       lr_scale, GuardArg{guard});
+        else if (guard)
+            T2V_LAUNCH(sgd_multi_k<GuardArg>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, momentum, gscale, first_step, GuardArg{guard});
+        else if (lr_scale)
             T2V_LAUNCH(sgd_multi_k<const float*>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, momentum, gscale, first_step, lr_scale);
         else
             T2V_LAUNCH(sgd_multi_k<>, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, lr, momentum, gscale, first_step);
@@ -2442,9 +2482,17 @@ extern "C" int t2v_sgd_multi_sched(const t2v_adam_job* jobs, int njobs, float lr
     if (!lr_scale) return T2V_EINVAL;
     return sgd_multi(jobs, njobs, lr, momentum, gscale, first_step, lr_scale, st);
 }
+extern "C" int t2v_sgd_multi_guard(const t2v_adam_job* jobs, int njobs, float lr, const float* lr_scale, float momentum, float gscale,
+                                   int first_step, const float* guard, void* st) {
+    if (!guard) return T2V_EINVAL;
+    return sgd_multi(jobs, njobs, lr, momentum, gscale, first_step, lr_scale, st, guard);
+}
 // step state {step, bc1, bc2}: step += 1 and the bias corrections 1 - beta^step, evaluated in double and
 // rounded to float exactly like the host path does (python float -> c_float).
-__global__ void adam_tick_k(float* state, float b1, float b2) {
+// (adam_tick_k<GuardArg>, t2v_adam_tick_guard: a skipped step does not count)
+template <typename... Guard>
+__global__ void adam_tick_k(float* state, float b1, float b2, Guard... guard) {
+    if constexpr (sizeof...(Guard) > 0) { if (guard_of(guard...)[1] != 0.f) return; }
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         const float t = state[0] + 1.f;
         state[0] = t;
@@ -2454,7 +2502,110 @@ __global__ void adam_tick_k(float* state, float b1, float b2) {
 }
 extern "C" int t2v_adam_tick(float* state, float b1, float b2, void* st) {
     if (!state) return T2V_EINVAL;
-    T2V_LAUNCH(adam_tick_k, dim3(1), dim3(64), 0, S_(st), state, b1, b2);
+    T2V_LAUNCH(adam_tick_k<>, dim3(1), dim3(64), 0, S_(st), state, b1, b2);
+    return launch_status();
+}
+extern "C" int t2v_adam_tick_guard(float* state, float b1, float b2, const float* guard, void* st) {
+    if (!state || !guard) return T2V_EINVAL;
+    T2V_LAUNCH(adam_tick_k<GuardArg>, dim3(1), dim3(64), 0, S_(st), state, b1, b2, GuardArg{guard});
+    return launch_status();
+}
+
+// ---------------------------------------------------------------- gradient guard (--grad_guard / --D_clip / --G_clip)
+// Global L2 norm of gscale * g over the gradients of one optimiser step, in two kinds of launch and without an atomic, a fence or a
+// memset: grad_sumsq_k has adam_multi_k's batching (64 tensors per launch, pointers by value, one block per 4096-element chunk,
+// the same binary search) and block b of a launch stores sum((g * gscale)^2) over its chunk to partials[chunk0 + b] — every slot
+// of the call is written on every call, with a plain store. Each thread adds its (at most 17) squares serially in element order,
+// then a 6-step wave64 shuffle and a 2-step sum of the four waves through LDS: a fixed order, so the bits repeat.
+struct SumsqBatch {
+    const float* g[ADAM_MT];
+    int n[ADAM_MT]; int begin[ADAM_MT + 1]; int njobs;
+};
+__global__ __launch_bounds__(256) void grad_sumsq_k(SumsqBatch tb, float gscale, float* __restrict__ partials, int chunk0) {
+    __shared__ float red[4];
+    int lo = 0, hi = tb.njobs;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tb.begin[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
+    const int j = lo;
+    const long base = (long)((int)blockIdx.x - tb.begin[j]) * ADAM_CHUNK;
+    const int len = (int)min((long)ADAM_CHUNK, (long)tb.n[j] - base);
+    const float* __restrict__ g = tb.g[j] + base;
+    const int nv = (((uintptr_t)g & 15) == 0) ? (len >> 2) : 0;
+    float acc = 0.f;
+    for (int q = threadIdx.x; q < nv; q += 256) {
+        const float4 G = ((const float4*)g)[q];
+        const float a = G.x * gscale, b = G.y * gscale, c = G.z * gscale, d = G.w * gscale;
+        acc += a * a; acc += b * b; acc += c * c; acc += d * d;
+    }
+    for (int i = nv * 4 + threadIdx.x; i < len; i += 256) {
+        const float a = g[i] * gscale;
+        acc += a * a;
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[(long)chunk0 + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+extern "C" int t2v_grad_sumsq_multi(const t2v_adam_job* jobs, int njobs, float gscale, float* partials, void* st) {
+    if (!jobs || njobs < 1 || !partials) return T2V_EINVAL;
+    long total = 0;
+    for (int i = 0; i < njobs; ++i) {
+        if (!jobs[i].g || jobs[i].n < 1 || jobs[i].n > 0x7fffffffL) return T2V_EINVAL;
+        total += (jobs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    }
+    if (total > 0x7fffffffL) return T2V_EINVAL;
+    long chunk0 = 0;
+    for (int at = 0; at < njobs; at += ADAM_MT) {
+        SumsqBatch tb;
+        const int cnt = njobs - at < ADAM_MT ? njobs - at : ADAM_MT;
+        long blocks = 0;
+        for (int i = 0; i < ADAM_MT; ++i) {
+            if (i < cnt) {
+                const t2v_adam_job& jb = jobs[at + i];
+                tb.g[i] = (const float*)jb.g; tb.n[i] = (int)jb.n; tb.begin[i] = (int)blocks;
+                blocks += (jb.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+            } else { tb.g[i] = nullptr; tb.n[i] = 0; tb.begin[i] = (int)blocks; }
+        }
+        tb.begin[ADAM_MT] = (int)blocks;
+        tb.njobs = cnt;
+        T2V_LAUNCH(grad_sumsq_k, dim3((unsigned)blocks), dim3(256), 0, S_(st), tb, gscale, partials, (int)chunk0);
+        chunk0 += blocks;
+    }
+    return launch_status();
+}
+// One block turns the partials into the decision. Thread t adds its contiguous run of partials in index order in double, thread 0
+// then adds the 256 runs in thread order: one fixed order for a given chunk count. norm = (float)sqrt(sum); a norm that is not
+// finite (a NaN or inf gradient, or squares past fp32's range in one chunk) sets skip. Otherwise, with clip > 0,
+// coef = clip / (norm + 1e-6f) where that is < 1 (torch.nn.utils.clip_grad_norm_) and exactly 1.0f where it is not.
+// state: {coef, skip, norm, steps, skipped, clipped, 0, 0}; the three counts are floats (exact to 2^24).
+__global__ __launch_bounds__(256) void grad_guard_k(const float* __restrict__ partials, int n, float clip, float* __restrict__ state) {
+    __shared__ double run[256];
+    const int per = (n + 255) / 256;
+    const int lo = min(n, (int)threadIdx.x * per), hi = min(n, lo + per);
+    double s = 0.0;
+    for (int i = lo; i < hi; ++i) s += (double)partials[i];
+    run[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int t = 0; t < 256; ++t) tot += run[t];
+        const float norm = (float)sqrt(tot);
+        const bool bad = !(fabsf(norm) <= 3.402823466e+38f);          // inf or NaN
+        float coef = 1.f;
+        if (!bad && clip > 0.f) {
+            const float c = clip / (norm + 1e-6f);
+            if (c < 1.f) coef = c;
+        }
+        state[0] = coef;
+        state[1] = bad ? 1.f : 0.f;
+        state[2] = norm;
+        state[3] = state[3] + 1.f;
+        if (bad) state[4] = state[4] + 1.f;
+        if (coef < 1.f) state[5] = state[5] + 1.f;
+    }
+}
+extern "C" int t2v_grad_guard(const float* partials, int nchunks, float clip, float* state, void* st) {
+    if (!partials || nchunks < 1 || !state || clip != clip) return T2V_EINVAL;
+    T2V_LAUNCH(grad_guard_k, dim3(1), dim3(256), 0, S_(st), partials, nchunks, clip, state);
     return launch_status();
 }
 // learning-rate schedule state {k, factor}: the factor of update k, i.e. of training iteration it = k / spi, in double

@@ -1499,15 +1499,27 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, step, gscale=1.0, step_dev=None):
           't2v_adam')
 
 
-def adam_step_multi(items, lr, b1, b2, eps, step, gscale=1.0, step_dev=None, lr_scale=None):
-    """`items`: [(p, g, exp_avg, exp_avg_sq)] that share `step` — one launch per 64 tensors (`t2v_adam_multi`). `lr_scale`: a
-    device-resident schedule state {k, factor} (gan.lr_sched) — the rate is lr * factor, read at run time (`t2v_adam_multi_sched`)."""
+def adam_jobs(items):
+    """[(p, g, exp_avg, exp_avg_sq)] as the t2v_adam_job array the multi-tensor launches take."""
     from ._lib import AdamJob
     arr = (AdamJob * len(items))()
     for a, (p, g, m, v) in zip(arr, items):
         a.p, a.g, a.m, a.v, a.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    return arr
+
+
+def adam_step_multi(items, lr, b1, b2, eps, step, gscale=1.0, step_dev=None, lr_scale=None, guard=None):
+    """`items`: [(p, g, exp_avg, exp_avg_sq)] that share `step` — one launch per 64 tensors (`t2v_adam_multi`). `lr_scale`: a
+    device-resident schedule state {k, factor} (gan.lr_sched) — the rate is lr * factor, read at run time (`t2v_adam_multi_sched`).
+    `guard`: a device-resident guard state (gan.grad_guard) — the step is skipped or its gradients scaled as the state says
+    (`t2v_adam_multi_guard`, with or without `lr_scale`)."""
+    arr = adam_jobs(items)
     bc1 = 1.0 - b1 ** step
     bc2 = 1.0 - b2 ** step
+    if guard is not None:
+        check(lib().t2v_adam_multi_guard(arr, len(items), lr, _p(lr_scale), b1, b2, eps, bc1, bc2, gscale, _p(step_dev), _p(guard),
+                                         _stream()), 't2v_adam_multi_guard')
+        return
     if lr_scale is not None:
         check(lib().t2v_adam_multi_sched(arr, len(items), lr, _p(lr_scale), b1, b2, eps, bc1, bc2, gscale, _p(step_dev), _stream()),
               't2v_adam_multi_sched')

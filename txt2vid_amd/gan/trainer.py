@@ -66,7 +66,7 @@ def _positive(kind, flag):
 def add_params_to_parser(parser):
     """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema,
     --G_ema_start, --D_aug, --D_aug_p, --D_ada, --D_ada_interval, --D_ada_kclips, --D_sn, --lr_decay, --lr_decay_iters,
-    --lr_decay_start and --lr_final are new."""
+    --lr_decay_start, --lr_final, --grad_guard, --D_clip and --G_clip are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
     parser.add_argument('--log_period', type=int, default=20)
@@ -121,6 +121,14 @@ def add_params_to_parser(parser):
                         help='(new) iterations at the full rate before the decay begins (default 0)')
     parser.add_argument('--lr_final', type=float, default=None, metavar='F',
                         help='(new) the fraction of the base rate that remains at the end, in [0, 1] (default 0)')
+    parser.add_argument('--grad_guard', action='store_true', default=False,
+                        help='(new) measure the global gradient norm in front of both optimiser steps, inside the replayed graph, '
+                             'and skip a step whose norm is inf or NaN (parameters, moments and step count stay as they are)')
+    parser.add_argument('--D_clip', type=float, default=None, metavar='C',
+                        help="(new) clip the discriminator's gradients to global L2 norm C > 0 "
+                             '(torch.nn.utils.clip_grad_norm_ semantics); implies --grad_guard')
+    parser.add_argument('--G_clip', type=float, default=None, metavar='C',
+                        help="(new) clip the generator's gradients to global L2 norm C > 0; implies --grad_guard")
     return parser
 
 
@@ -677,6 +685,9 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
     # iteration the device state stood at when training started (read once, here)
     lr_sched = getattr(getattr(optD, 'lr_sched', None), 'sched', None)
     lr_it0 = lr_sched.counters()['D'] // lr_sched.spi['D'] if lr_sched is not None else 0
+    # --grad_guard / --D_clip / --G_clip: norms, coefficients and counts of the last optimiser steps, printed at the log period
+    guard = getattr(getattr(optD, 'grad_guard', None), 'guard', None)
+    guard_rows = None
     avg_iter = RollingAvg(window_size=max(1, params.log_period))
     avg_load = RollingAvg(window_size=max(1, params.log_period))
     load_watch, iter_watch = Stopwatch(), Stopwatch()
@@ -730,7 +741,9 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 # copies). The rolling averages lag by one iteration.
                 lKL = graphed.ts.lKL
                 if loss_ring is None:
-                    loss_ring = [(torch.empty(4, device=lD.device), torch.zeros(4).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+                    width = 4 if guard is None else 16      # (the guard's two states travel behind the four scalars)
+                    loss_ring = [(torch.empty(width, device=lD.device), torch.zeros(width).pin_memory(), torch.cuda.Event())
+                                 for _ in range(2)]
                 dbuf, hbuf, ev = loss_ring[iteration & 1]
                 if _X_BY_MEMCPY:
                     TF.copy_into(lD.reshape(1), dbuf[0:1])
@@ -739,6 +752,9 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                         TF.copy_into(lKL.reshape(1), dbuf[2:3])
                     if ada is not None:
                         TF.copy_into(ada.p, dbuf[3:4])
+                    if guard is not None:
+                        TF.copy_into(guard.state['D'][:6], dbuf[4:10])
+                        TF.copy_into(guard.state['G'][:6], dbuf[10:16])
                     hbuf.copy_(dbuf, non_blocking=True)
                 else:                                    # copy kernels writing the pinned buffer in place: no copy-engine hop behind the graph
                     TF._copy2d(lD.reshape(1), 0, 1, hbuf, 0, 1, 1, 1)
@@ -747,6 +763,9 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                         TF._copy2d(lKL.reshape(1), 0, 1, hbuf, 2, 1, 1, 1)
                     if ada is not None:
                         TF._copy2d(ada.p, 0, 1, hbuf, 3, 1, 1, 1)     # (travels with the losses: no sync of its own)
+                    if guard is not None:
+                        TF._copy2d(guard.state['D'], 0, 6, hbuf, 4, 6, 1, 6)      # (likewise)
+                        TF._copy2d(guard.state['G'], 0, 6, hbuf, 10, 6, 1, 6)
                 ev.record()
                 if pending is not None:
                     pending[1].synchronize()
@@ -756,6 +775,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                         kl_loss.update(float(pending[0][2]))
                     if ada is not None:
                         ada_p = float(pending[0][3])
+                    if guard is not None:
+                        guard_rows = (pending[0][4:10].tolist(), pending[0][10:16].tolist())
                 pending = (hbuf, ev)
             else:
                 ts = TrainStep(gan, optD, optG, losses, params, device, end2end, grad_sync)       # (= train_iteration)
@@ -766,6 +787,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                     kl_loss.update(float(ts.lKL))
                 if ada is not None and params.log_period > 0 and iteration % params.log_period == 0:
                     ada_p = float(ada.p)
+                if guard is not None and params.log_period > 0 and iteration % params.log_period == 0:
+                    guard_rows = (guard.state['D'].tolist(), guard.state['G'].tolist())
             # checkpoint: the reference tests `save_example_period` here (trainer.py:269) and never reads
             # --save_model_period; the intended flag is used (SURVEY §8a defect 3).
             if writer and ((iteration == 1 and params.save_initial) or (params.save_model_period > 0 and
@@ -776,6 +799,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 to_save.update(gan.save_dict())
                 if lr_sched is not None:
                     to_save['lr_sched'] = lr_sched.state_dict()
+                if guard is not None:
+                    to_save['grad_guard'] = guard.state_dict()
                 torch.save(to_save, '%s/iter_%d_lossG_%.4f_lossD_%.4f' % (params.out, iteration, gen_loss.get(),
                                                                           discrim_loss.get()))
             if params.log_period > 0 and iteration % params.log_period == 0:
@@ -794,6 +819,9 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                     f = lr_sched.factor(it)
                     status('Iter %d, learning rates (--lr_decay %s, iteration %d of the schedule, factor %.6g): D %.6g G %.6g' % (
                         iteration, lr_sched.kind, it + 1, f, optD.param_groups[0]['lr'] * f, optG.param_groups[0]['lr'] * f))
+                if guard_rows is not None:
+                    from .grad_guard import log_line, unpack
+                    status(log_line(iteration, unpack(guard_rows[0]), unpack(guard_rows[1])))
                 torch.cuda.reset_peak_memory_stats()
             if writer and params.save_example_period > 0 and ((iteration == 1 and params.save_initial_examples) or
                                                               iteration % params.save_example_period == 0):

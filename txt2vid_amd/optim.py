@@ -51,10 +51,19 @@ class Adam(torch.optim.Optimizer):
         self.step_dev = None          # device-resident step counter (set by `make_capturable`)
         self.weight_hook = None       # gan.spectral.SpectralNorm of this optimiser's weights (--D_sn), or None
         self.lr_sched = None          # gan.lr_sched.OptSchedule: this optimiser's side of --lr_decay, or None
+        self.grad_guard = None        # gan.grad_guard.OptGuard: this optimiser's side of --grad_guard / --*_clip, or None
 
     def make_capturable(self, device):
         """Keep the step number on the device so that a captured HIP graph applies the right bias
         corrections on every replay (all parameters of this optimiser step together)."""
+        if getattr(self, 'grad_guard', None) is not None and self.step_dev is not None:
+            # under a gradient guard the device counter is the only one that knows which steps were skipped: it stays where it
+            # is (the same memory), and the host-side entries follow it
+            n = int(self.step_dev[0].item())
+            for st in self.state.values():
+                if st:
+                    st['step'] = n
+            return
         steps = [int(self.state[p]['step']) for g in self.param_groups for p in g['params'] if p in self.state and self.state[p]]
         if len({tuple(g['betas']) for g in self.param_groups}) != 1:
             raise NotImplementedError('graph capture: one (beta1, beta2) per optimiser')
@@ -73,6 +82,12 @@ class Adam(torch.optim.Optimizer):
         moments as dense arrays through raw pointers, so anything that is not a dense tensor of its own is re-materialised."""
         super().load_state_dict(state_dict)
         _densify_state(self)
+        if getattr(self, 'grad_guard', None) is not None and self.step_dev is not None:
+            # the device counter is authoritative under a gradient guard: it takes the loaded step number, in place
+            steps = [int(st['step']) for st in self.state.values() if st]
+            n = max(steps) if steps else 0
+            b1, b2 = self.param_groups[0]['betas']
+            self.step_dev.copy_(torch.tensor([float(n), 1.0 - b1 ** n, 1.0 - b2 ** n], dtype=torch.float32))
 
     def state_dict(self):
         """Same layout as torch.optim.Adam. Under graph replay the step counter advances on the device only: fold it back
@@ -89,13 +104,11 @@ class Adam(torch.optim.Optimizer):
         TF.grad_sink_flush()                  # (no-op unless a backward pass left k-split partial sums pending)
         if self.weight_hook is not None:
             self.weight_hook.project_grads()  # spectral norm: dL/dWhat -> dL/dW, and the master W back into the parameters
-        if self.step_dev is not None:
-            b1, b2 = self.param_groups[0]['betas']
-            TF.check(TF.lib().t2v_adam_tick(TF._p(self.step_dev), b1, b2, TF._stream()), 't2v_adam_tick')
         sched = getattr(self, 'lr_sched', None)
-        if sched is not None:
-            sched.tick()                      # --lr_decay: this update's factor into device memory, eager and captured alike
-        touched = []
+        guard = getattr(self, 'grad_guard', None)
+        if guard is None:
+            self._tick(sched, None)
+        touched, launches = [], []
         for group in self.param_groups:
             b1, b2 = group['betas']
             by_step = {}                      # tensors that have taken the same number of steps update in one launch
@@ -124,9 +137,20 @@ class Adam(torch.optim.Optimizer):
                         raise ValueError('parameter layout not supported by the fused optimiser: strides %s' % (p.stride(),))
                     by_step.setdefault(st['step'], []).append((p, g, st['exp_avg'], st['exp_avg_sq']))
                 touched.append(p)
-            for step, items in by_step.items():
-                TF.adam_step_multi(items, group['lr'], b1, b2, group['eps'], step, self.grad_scale, self.step_dev,
-                                   None if sched is None else sched.state)
+            launches += [(group, step, items) for step, items in by_step.items()]
+        if guard is not None:
+            # --grad_guard / --*_clip: the norm of exactly the gradients the launches below read, the decision, then the ticks
+            # (the step counter stands still on a skipped step; the schedule counts iterations and moves on regardless)
+            every = [it for _, _, items in launches for it in items]
+            if every:
+                guard.measure(TF.adam_jobs(every), len(every), self.grad_scale)
+            else:
+                guard = None                  # nothing to update: nothing to measure, a plain tick
+            self._tick(sched, guard)
+        for group, step, items in launches:
+            b1, b2 = group['betas']
+            TF.adam_step_multi(items, group['lr'], b1, b2, group['eps'], step, self.grad_scale, self.step_dev,
+                               None if sched is None else sched.state, None if guard is None else guard.state)
         if self.weight_hook is not None:
             # spectral norm: the parameters hold W / sigma again before they are re-packed — EVERY normalised weight does, also one
             # that had no gradient in this step (u, v and sigma moved on), so all of them join the re-pack
@@ -134,6 +158,18 @@ class Adam(torch.optim.Optimizer):
         TF.bump_weight_epoch(touched)   # their packed weights are stale ...
         TF.repack_params(touched)       # ... refresh them in place right away (same addresses for graph replay)
         return None
+
+
+    def _tick(self, sched, guard):
+        if self.step_dev is not None:
+            b1, b2 = self.param_groups[0]['betas']
+            if guard is not None:
+                TF.check(TF.lib().t2v_adam_tick_guard(TF._p(self.step_dev), b1, b2, TF._p(guard.state), TF._stream()),
+                         't2v_adam_tick_guard')
+            else:
+                TF.check(TF.lib().t2v_adam_tick(TF._p(self.step_dev), b1, b2, TF._stream()), 't2v_adam_tick')
+        if sched is not None:
+            sched.tick()                      # --lr_decay: this update's factor into device memory, eager and captured alike
 
 
 class SGD(torch.optim.Optimizer):
@@ -147,6 +183,7 @@ class SGD(torch.optim.Optimizer):
         self.grad_scale = 1.0
         self.weight_hook = None       # as in Adam
         self.lr_sched = None          # as in Adam
+        self.grad_guard = None        # as in Adam
 
     def make_capturable(self, device):
         """Nothing step-dependent lives on the host once the momentum buffers exist (they do after the eager warm-up)."""
@@ -162,9 +199,10 @@ class SGD(torch.optim.Optimizer):
         if self.weight_hook is not None:
             self.weight_hook.project_grads()
         sched = getattr(self, 'lr_sched', None)
-        if sched is not None:
+        guard = getattr(self, 'grad_guard', None)
+        if sched is not None and guard is None:
             sched.tick()
-        touched = []
+        touched, launches = [], []
         for group in self.param_groups:
             mu = float(group['momentum'])
             first, later = [], []
@@ -175,23 +213,43 @@ class SGD(torch.optim.Optimizer):
                 g = p.grad
                 if g.stride() != p.stride():             # one flat index over p, g and the momentum buffer
                     g = torch.empty_strided(p.shape, p.stride(), dtype=p.dtype, device=p.device).copy_(g)
-                if mu != 0 and 'momentum_buffer' not in st:
+                if mu != 0 and 'momentum_buffer' not in st and guard is not None:
+                    # under a gradient guard the first step may be the skipped one: the buffer starts as zeros and every launch
+                    # is the `first = 0` form (mu * 0 + g == g), so nothing is ever left uninitialised
+                    st['momentum_buffer'] = TF.zeros_like(p)
+                    later.append((p, g, st['momentum_buffer']))
+                elif mu != 0 and 'momentum_buffer' not in st:
                     st['momentum_buffer'] = torch.empty_like(p, memory_format=torch.preserve_format)
                     first.append((p, g, st['momentum_buffer']))
                 else:
                     _check_state_layout(self, p, st, ('momentum_buffer',))
                     later.append((p, g, st.get('momentum_buffer')))
                 touched.append(p)
-            for items, is_first in ((first, 1), (later, 0)):
-                if not items:
-                    continue
-                arr = (AdamJob * len(items))()
-                for a, (p, g, m) in zip(arr, items):
-                    a.p, a.g, a.m, a.v, a.n = p.data_ptr(), g.data_ptr(), (m.data_ptr() if m is not None else None), None, p.numel()
-                if sched is not None:
-                    TF.check(TF.lib().t2v_sgd_multi_sched(arr, len(items), group['lr'], TF._p(sched.state), mu, self.grad_scale,
-                                                          is_first, TF._stream()), 't2v_sgd_multi_sched')
-                    continue
+            launches += [(group, mu, items, is_first) for items, is_first in ((first, 1), (later, 0)) if items]
+
+        def jobs(items):
+            arr = (AdamJob * len(items))()
+            for a, (p, g, m) in zip(arr, items):
+                a.p, a.g, a.m, a.v, a.n = p.data_ptr(), g.data_ptr(), (m.data_ptr() if m is not None else None), None, p.numel()
+            return arr
+        if guard is not None:
+            every = [it for _, _, items, _ in launches for it in items]
+            if every:
+                guard.measure(jobs(every), len(every), self.grad_scale)
+            else:
+                guard = None
+            if sched is not None:
+                sched.tick()
+        for group, mu, items, is_first in launches:
+            arr = jobs(items)
+            if guard is not None:
+                TF.check(TF.lib().t2v_sgd_multi_guard(arr, len(items), group['lr'], None if sched is None else TF._p(sched.state),
+                                                      mu, self.grad_scale, is_first, TF._p(guard.state), TF._stream()),
+                         't2v_sgd_multi_guard')
+            elif sched is not None:
+                TF.check(TF.lib().t2v_sgd_multi_sched(arr, len(items), group['lr'], TF._p(sched.state), mu, self.grad_scale,
+                                                      is_first, TF._stream()), 't2v_sgd_multi_sched')
+            else:
                 TF.check(TF.lib().t2v_sgd_multi(arr, len(items), group['lr'], mu, self.grad_scale, is_first, TF._stream()),
                          't2v_sgd_multi')
         if self.weight_hook is not None:

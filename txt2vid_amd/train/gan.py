@@ -41,6 +41,8 @@ def main(args):
     check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
     from ..gan import lr_sched
     lr_sched.check_args(args)            # --lr_decay: likewise refused here, before a process group forms
+    from ..gan import grad_guard
+    grad_guard.check_args(args)          # --grad_guard / --D_clip / --G_clip: likewise
     from .. import dist as tdist
     rank, world = tdist.init_from_env('nccl')
     from ..util.misc import limit_host_threads
@@ -95,7 +97,7 @@ def main(args):
     else:
         optD = Adam(D_params, lr=args.D_lr, betas=(args.D_beta1, args.D_beta2))
         optG = Adam(G_params, lr=args.G_lr, betas=(args.G_beta1, args.G_beta2))
-    resumed_rng, resumed_iter, resumed_ema, resumed_sn, resumed_lr = None, 0, None, None, None
+    resumed_rng, resumed_iter, resumed_ema, resumed_sn, resumed_lr, resumed_guard = None, 0, None, None, None, None
     gan = CondGan(gen=gen, discrims=discrims, cond_encoder=txt_encoder, discrim_names=args.D_names,
                   discrim_lambdas=args.D_lambdas, gp_scale=float(world))
     if args.D_ada is not None:
@@ -116,6 +118,7 @@ def main(args):
         if 'gen_ema' in to_load and args.G_ema > 0:
             resumed_ema = (to_load['gen_ema'], to_load.get('gen_ema_updates', 0))
         resumed_lr = to_load.get('lr_sched')
+        resumed_guard = to_load.get('grad_guard')
         del to_load
     if gan.ada is not None:
         st = gan.ada.ada.tolist()
@@ -132,6 +135,22 @@ def main(args):
             args.lr_decay, args.lr_decay_start, args.lr_decay_iters, args.lr_final, k['D'], k['G']))
     elif resumed_lr is not None:
         status('the checkpoint holds a learning-rate schedule state (%s); without --lr_decay it is ignored' % (resumed_lr,))
+    if grad_guard.enabled(args):
+        # gradient clipping and the non-finite guard inside the replayed graph (not in the reference): eight floats of device state
+        # per optimiser, the counts saved under the checkpoint's key 'grad_guard'. Gradients are identical on every rank after the
+        # exchange and the reduction is deterministic, so every rank takes the same decision: no exchange of its own
+        guard = grad_guard.GradGuard(args.D_clip, args.G_clip, device).attach(optD, optG)
+        if args.weights is not None:
+            for note in guard.load_state_dict(resumed_guard):
+                status('Gradient guard: ' + note)
+        k = guard.counters()
+        status('Gradient guard: D clip %s, G clip %s, non-finite steps are skipped; D %d steps (%d skipped, %d clipped), '
+               'G %d steps (%d skipped, %d clipped) so far' % (
+                   'off' if args.D_clip is None else '%g' % args.D_clip, 'off' if args.G_clip is None else '%g' % args.G_clip,
+                   k['D']['steps'], k['D']['skipped'], k['D']['clipped'], k['G']['steps'], k['G']['skipped'], k['G']['clipped']))
+    elif resumed_guard is not None:
+        status('the checkpoint holds gradient-guard counts (%s); without --grad_guard / --D_clip / --G_clip the key is ignored'
+               % (resumed_guard,))
     if world > 1:
         # replicas bit-identical before the first step (whatever each rank's init / checkpoint read produced), then per-rank
         # generators for everything drawn per iteration (z, sub-sample phases, GP alphas, caption permutations)
