@@ -61,6 +61,7 @@ class AdaState(object):
         host[0] = self.p0
         self.ada = host.to(device)                     # (by copy: no fill kernel)
         self.p = self.ada[0:1]
+        self.slots, self.key = [('ada.p', self.p, 1)], None            # gan/extras.py: p travels with the losses
 
     def observe(self, u_r, u_f):
         """One D step's unconditional real / generated logits (a list per pyramid level, or one tensor) into the window, and the
@@ -82,6 +83,10 @@ class AdaState(object):
         if not math.isfinite(step):
             raise ValueError('step %r is not finite' % step)
         check(lib().t2v_ada_update(self.ada.data_ptr(), arr, len(rs), self.target, step, self.interval, _stream()), 't2v_ada_update')
+
+    def log_lines(self, iteration, values):
+        return ['Iter %d, augmentation probability p (--D_ada, target %g): %.4f' % (iteration, self.target, p[0])
+                for p in [values.get('ada.p')] if p]
 
     def state_dict(self):
         return {'ada': self.ada.detach().to('cpu', torch.float32).clone()}

@@ -114,6 +114,7 @@ class GradGuard(object):
         # made once (by copy: no fill kernel) and only ever written in place: captured graphs keep the addresses
         self.state = {w: torch.tensor([1.0] + [0.0] * 7, dtype=torch.float32).to(device) for w in ('D', 'G')}
         self.opts = {}
+        self.slots, self.key = [('guard.' + w, self.state[w], 6) for w in ('D', 'G')], 'grad_guard'       # gan/extras.py
 
     def attach(self, optD, optG):
         for w, opt in (('D', optD), ('G', optG)):
@@ -124,6 +125,9 @@ class GradGuard(object):
                 # (also for eager runs) and is authoritative
                 opt.make_capturable(self.state[w].device)
         return self
+
+    def log_lines(self, iteration, values):
+        return [log_line(iteration, unpack(values['guard.D']), unpack(values['guard.G']))] if 'guard.D' in values else []
 
     def config(self):
         return {'clip_D': self.clip['D'], 'clip_G': self.clip['G']}

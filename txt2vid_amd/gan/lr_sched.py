@@ -84,6 +84,8 @@ class OptSchedule(object):
 class LrSchedule(object):
     """The configuration, the two device states and the host mirror. `n_d` / `n_g`: optimiser steps per iteration of D and G."""
 
+    slots, key = (), 'lr_sched'          # gan/extras.py: nothing to read with the losses; the checkpoint key
+
     def __init__(self, kind, end, start=0, final=0.0, n_d=1, n_g=1, device='cpu'):
         if kind not in KINDS:
             raise ValueError('unknown schedule %r (one of %s)' % (kind, ', '.join(sorted(KINDS))))
@@ -100,7 +102,14 @@ class LrSchedule(object):
 
     def attach(self, optD, optG):
         optD.lr_sched, optG.lr_sched = OptSchedule(self, 'D'), OptSchedule(self, 'G')
+        self.opts, self.it0 = {'D': optD, 'G': optG}, 0     # (it0: set when train() starts, extras.training_extras)
         return self
+
+    def log_lines(self, iteration, values):
+        it = self.it0 + iteration - 1
+        f = self.factor(it)                                    # the host mirror of the formula: nothing is read from the device
+        return ['Iter %d, learning rates (--lr_decay %s, iteration %d of the schedule, factor %.6g): D %.6g G %.6g' % (
+            iteration, self.kind, it + 1, f, self.opts['D'].param_groups[0]['lr'] * f, self.opts['G'].param_groups[0]['lr'] * f)]
 
     # ---- host mirror ---------------------------------------------------------------------------------------------------------
     def factor(self, it):

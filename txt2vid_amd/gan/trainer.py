@@ -1,6 +1,7 @@
 """Training loop of the TGANv2 hot path — same entry points and flags as txt2vid/gan/trainer.py
 (`add_params_to_parser`, `train`, `test`), with the loop body factored into `train_iteration` so that
-bench.py and the parity tests drive exactly what `train()` runs.
+bench.py and the parity tests drive exactly what `train()` runs. `train()` meets the opt-in features that log or are read with the
+losses (ada, lr schedule, gradient guard) through gan/extras.py and names none of them.
 
 Random draws follow the reference order on the HOST generators (SURVEY §7 "RNG parity"): 4x Subsample
 phase (trainer.py:157-158), z (trainer.py:221, drawn on the CPU and copied), 3x Subsample in G,
@@ -22,6 +23,7 @@ from ..util.dir import ensure_exists
 from ..util.log import status
 from ..util.metrics import RollingAvg
 from ..util.stopwatch import Stopwatch
+from .extras import LOSSES, Readout, training_extras
 
 
 def _ema_decay(text):
@@ -677,17 +679,9 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
         params.sample_batch_size = params.batch_size
     ensure_exists(params.out)
     ensure_exists(params.out_samples)
-    gen_loss = RollingAvg(window_size=params.loss_window_size)
-    discrim_loss = RollingAvg(window_size=params.loss_window_size)
-    kl_loss = RollingAvg(window_size=params.loss_window_size) if getattr(gan.gen, 'ca_dim', 0) else None     # conditioning augmentation
-    ada, ada_p = getattr(gan, 'ada', None), None             # --D_ada: p is read with the losses and printed at the log period
-    # --lr_decay: the rates printed at the log period come from the host mirror of the formula, counted on from the schedule
-    # iteration the device state stood at when training started (read once, here)
-    lr_sched = getattr(getattr(optD, 'lr_sched', None), 'sched', None)
-    lr_it0 = lr_sched.counters()['D'] // lr_sched.spi['D'] if lr_sched is not None else 0
-    # --grad_guard / --D_clip / --G_clip: norms, coefficients and counts of the last optimiser steps, printed at the log period
-    guard = getattr(getattr(optD, 'grad_guard', None), 'guard', None)
-    guard_rows = None
+    avg = {name: RollingAvg(window_size=params.loss_window_size) for name in LOSSES}     # (kl: conditioning augmentation only)
+    # the opt-in features that log or travel with the losses (gan/extras.py), and the host values last read for them
+    extras, seen = training_extras(gan, optD, optG), {}
     avg_iter = RollingAvg(window_size=max(1, params.log_period))
     avg_load = RollingAvg(window_size=max(1, params.log_period))
     load_watch, iter_watch = Stopwatch(), Stopwatch()
@@ -698,7 +692,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
     # HIP-graph replay of the iteration (see GraphedTrainStep) unless --no_graph / --end2end: the eager loop is
     # host-bound (~1 000 launches at ~20 us of Python each)
     use_graph = not end2end and not getattr(params, 'no_graph', False) and torch.device(device).type == 'cuda'
-    graphed, graphed_key, pending, loss_ring, graphed_encoder = None, None, None, None, None
+    graphed, graphed_key, graphed_encoder = None, None, None
+    readout = Readout(extras, device, by_memcpy=_X_BY_MEMCPY) if use_graph else None
     for epoch in range(num_epoch):
         if params.log_period > 0:
             status('Epoch %d started' % (epoch + 1))
@@ -736,59 +731,19 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                         status('HIP-graph replay of the iteration for batches of shape %s (2 eager iterations, then capture)' % (key[0],))
                 lD, lG = graphed.step(x, cond)
                 fake, xs = graphed.ts.fake, graphed.ts.xs
-                # Read the losses ONE iteration late, through a pinned buffer and an event: the host goes on to prepare
-                # and launch the next iteration while this one runs (the replay overwrites its loss scalars, hence the
-                # copies). The rolling averages lag by one iteration.
-                lKL = graphed.ts.lKL
-                if loss_ring is None:
-                    width = 4 if guard is None else 16      # (the guard's two states travel behind the four scalars)
-                    loss_ring = [(torch.empty(width, device=lD.device), torch.zeros(width).pin_memory(), torch.cuda.Event())
-                                 for _ in range(2)]
-                dbuf, hbuf, ev = loss_ring[iteration & 1]
-                if _X_BY_MEMCPY:
-                    TF.copy_into(lD.reshape(1), dbuf[0:1])
-                    TF.copy_into(lG.reshape(1), dbuf[1:2])
-                    if lKL is not None:
-                        TF.copy_into(lKL.reshape(1), dbuf[2:3])
-                    if ada is not None:
-                        TF.copy_into(ada.p, dbuf[3:4])
-                    if guard is not None:
-                        TF.copy_into(guard.state['D'][:6], dbuf[4:10])
-                        TF.copy_into(guard.state['G'][:6], dbuf[10:16])
-                    hbuf.copy_(dbuf, non_blocking=True)
-                else:                                    # copy kernels writing the pinned buffer in place: no copy-engine hop behind the graph
-                    TF._copy2d(lD.reshape(1), 0, 1, hbuf, 0, 1, 1, 1)
-                    TF._copy2d(lG.reshape(1), 0, 1, hbuf, 1, 1, 1, 1)
-                    if lKL is not None:
-                        TF._copy2d(lKL.reshape(1), 0, 1, hbuf, 2, 1, 1, 1)
-                    if ada is not None:
-                        TF._copy2d(ada.p, 0, 1, hbuf, 3, 1, 1, 1)     # (travels with the losses: no sync of its own)
-                    if guard is not None:
-                        TF._copy2d(guard.state['D'], 0, 6, hbuf, 4, 6, 1, 6)      # (likewise)
-                        TF._copy2d(guard.state['G'], 0, 6, hbuf, 10, 6, 1, 6)
-                ev.record()
-                if pending is not None:
-                    pending[1].synchronize()
-                    discrim_loss.update(float(pending[0][0]))
-                    gen_loss.update(float(pending[0][1]))
-                    if kl_loss is not None:
-                        kl_loss.update(float(pending[0][2]))
-                    if ada is not None:
-                        ada_p = float(pending[0][3])
-                    if guard is not None:
-                        guard_rows = (pending[0][4:10].tolist(), pending[0][10:16].tolist())
-                pending = (hbuf, ev)
+                # the losses and the extras' floats are read ONE iteration late (Readout): the rolling averages lag by one
+                readout.push(iteration, lD=lD, lG=lG, kl=graphed.ts.lKL)
+                got = readout.pop() or {}
             else:
                 ts = TrainStep(gan, optD, optG, losses, params, device, end2end, grad_sync)       # (= train_iteration)
                 lD, lG, fake, xs = ts.run(x, cond)
-                discrim_loss.update(float(lD))
-                gen_loss.update(float(lG))
-                if kl_loss is not None:
-                    kl_loss.update(float(ts.lKL))
-                if ada is not None and params.log_period > 0 and iteration % params.log_period == 0:
-                    ada_p = float(ada.p)
-                if guard is not None and params.log_period > 0 and iteration % params.log_period == 0:
-                    guard_rows = (guard.state['D'].tolist(), guard.state['G'].tolist())
+                got = {name: [float(t)] for name, t in zip(LOSSES, (lD, lG, ts.lKL)) if t is not None}
+                if params.log_period > 0 and iteration % params.log_period == 0:         # the extras' slots, read on the spot
+                    got.update({name: t[:n].tolist() for e in extras for name, t, n in e.slots})
+            for name in LOSSES:
+                if name in got:
+                    avg[name].update(got.pop(name)[0])
+            seen.update(got)
             # checkpoint: the reference tests `save_example_period` here (trainer.py:269) and never reads
             # --save_model_period; the intended flag is used (SURVEY §8a defect 3).
             if writer and ((iteration == 1 and params.save_initial) or (params.save_model_period > 0 and
@@ -796,39 +751,28 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 from ..train.setup import get_rng_state
                 # extra keys next to the reference's layout (its loader ignores them; its files, which lack them, still load here)
                 to_save = {'optG': optG.state_dict(), 'optD': optD.state_dict(), 'iteration': iteration, 'rng_state': get_rng_state()}
-                to_save.update(gan.save_dict())
-                if lr_sched is not None:
-                    to_save['lr_sched'] = lr_sched.state_dict()
-                if guard is not None:
-                    to_save['grad_guard'] = guard.state_dict()
-                torch.save(to_save, '%s/iter_%d_lossG_%.4f_lossD_%.4f' % (params.out, iteration, gen_loss.get(),
-                                                                          discrim_loss.get()))
+                to_save.update(gan.save_dict())          # (with the keys of the extras the models own)
+                to_save.update({e.key: e.state_dict() for e in extras if e.key})
+                torch.save(to_save, '%s/iter_%d_lossG_%.4f_lossD_%.4f' % (params.out, iteration, avg['lG'].get(), avg['lD'].get()))
             if params.log_period > 0 and iteration % params.log_period == 0:
                 sys.stdout.flush()
                 status('[%d/%d; %d/%d] - Iter %d, Loss_D: %.4f Loss_G: %.4f (%.2fGB used; %.2fGB cached) - %.4f sec/iter; '
-                       '%.4f sec/batch load' % (epoch, num_epoch, i, len(dataset), iteration, discrim_loss.get(),
-                                                gen_loss.get(), torch.cuda.max_memory_allocated() / 1e9,
+                       '%.4f sec/batch load' % (epoch, num_epoch, i, len(dataset), iteration, avg['lD'].get(),
+                                                avg['lG'].get(), torch.cuda.max_memory_allocated() / 1e9,
                                                 torch.cuda.max_memory_reserved() / 1e9, avg_iter.get(), avg_load.get()))
-                if kl_loss is not None:
+                if getattr(gan.gen, 'ca_dim', 0):
                     status('Iter %d, KL (conditioning augmentation, inside Loss_G with weight %g): %.4f' %
-                           (iteration, gan.gen.ca_kl_coeff, kl_loss.get()))
-                if ada_p is not None:
-                    status('Iter %d, augmentation probability p (--D_ada, target %g): %.4f' % (iteration, ada.target, ada_p))
-                if lr_sched is not None:
-                    it = lr_it0 + iteration - 1
-                    f = lr_sched.factor(it)
-                    status('Iter %d, learning rates (--lr_decay %s, iteration %d of the schedule, factor %.6g): D %.6g G %.6g' % (
-                        iteration, lr_sched.kind, it + 1, f, optD.param_groups[0]['lr'] * f, optG.param_groups[0]['lr'] * f))
-                if guard_rows is not None:
-                    from .grad_guard import log_line, unpack
-                    status(log_line(iteration, unpack(guard_rows[0]), unpack(guard_rows[1])))
+                           (iteration, gan.gen.ca_kl_coeff, avg['kl'].get()))
+                for e in extras:
+                    for line in e.log_lines(iteration, seen):
+                        status(line)
                 torch.cuda.reset_peak_memory_stats()
             if writer and params.save_example_period > 0 and ((iteration == 1 and params.save_initial_examples) or
                                                               iteration % params.save_example_period == 0):
                 from .samples import save_frames, save_sentences
                 status('saving to %s (iteration %d)' % (params.out_samples, iteration))
                 save_frames(xs[0], '%s/real_samples.png' % params.out_samples)
-                if getattr(gan, 'gen_ema', None) is not None:
+                if gan.gen_ema is not None:
                     step = graphed.ts if use_graph else ts
                     fake = _averaged_samples(gan, step._z, None if step.conds is None else step.conds[0])
                     status('fake samples of iteration %d come from the averaged generator (%d updates)' % (iteration,

@@ -1,5 +1,6 @@
 """Adam on the fused HIP kernel — drop-in for the `torch.optim.Adam(params, lr, betas)` call sites of
-txt2vid/train/gan.py:93-94 (same defaults, same `state_dict()` layout: step / exp_avg / exp_avg_sq)."""
+txt2vid/train/gan.py:93-94 (same defaults, same `state_dict()` layout: step / exp_avg / exp_avg_sq) — and SGD for `--sgd`.
+`_FusedOptimizer.step` states the order of a step's launches once (tests/test_optim_step_cpu.py pins it)."""
 import torch
 
 from . import functional as TF
@@ -42,27 +43,72 @@ def _check_state_layout(opt, p, st, keys):
     seen[id(p)] = sig
 
 
-class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
-        if weight_decay != 0:
-            raise NotImplementedError('the hot path uses no weight decay')
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+class _FusedOptimizer(torch.optim.Optimizer):
+    """What Adam and SGD share: the attributes the opt-in features hang on and the skeleton of the step. A subclass collects its
+    launches (`_collect`), builds the job table the guard measures (`_jobs`) and updates (`_launch`); Adam adds its tick (`_tick`)."""
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         self.grad_scale = 1.0
-        self.step_dev = None          # device-resident step counter (set by `make_capturable`)
         self.weight_hook = None       # gan.spectral.SpectralNorm of this optimiser's weights (--D_sn), or None
         self.lr_sched = None          # gan.lr_sched.OptSchedule: this optimiser's side of --lr_decay, or None
         self.grad_guard = None        # gan.grad_guard.OptGuard: this optimiser's side of --grad_guard / --*_clip, or None
 
+    def load_state_dict(self, state_dict):
+        """torch's loader keeps the strides of the checkpoint's tensors; the kernels walk dense arrays: re-materialise the rest."""
+        super().load_state_dict(state_dict)
+        _densify_state(self)
+
+    def _tick(self, sched, guard):
+        if sched is not None:
+            sched.tick()                      # --lr_decay: this update's factor into device memory, eager and captured alike
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        TF.grad_sink_flush()                  # (no-op unless a backward pass left k-split partial sums pending)
+        if self.weight_hook is not None:
+            self.weight_hook.project_grads()  # spectral norm: dL/dWhat -> dL/dW, and the master W back into the parameters
+        sched, guard = getattr(self, 'lr_sched', None), self.grad_guard      # (test_lr_sched_gpu strips `lr_sched` for its baseline)
+        if guard is None:
+            self._tick(sched, None)
+        touched, launches = self._collect(guard)
+        if guard is not None:
+            # the norm of exactly the gradients the launches below read, the decision, then the ticks (Adam's step counter
+            # stands still on a skipped step; the schedule counts iterations and moves on regardless)
+            every = [it for launch in launches for it in launch[0]]
+            if every:
+                guard.measure(self._jobs(every), len(every), self.grad_scale)
+            else:
+                guard = None                  # nothing to update: nothing to measure, a plain tick
+            self._tick(sched, guard)
+        for launch in launches:
+            self._launch(sched, guard, *launch)
+        if self.weight_hook is not None:
+            # spectral norm: EVERY normalised weight holds W / sigma again (also one without a gradient): all join the re-pack
+            touched = self.weight_hook.refresh(touched)
+        TF.bump_weight_epoch(touched)   # their packed weights are stale ...
+        TF.repack_params(touched)       # ... refresh them in place right away (same addresses for graph replay)
+
+
+class Adam(_FusedOptimizer):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        if weight_decay != 0:
+            raise NotImplementedError('the hot path uses no weight decay')
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.step_dev = None          # device-resident step counter (set by `make_capturable`)
+
+    def _set_steps(self, n):
+        for st in self.state.values():
+            if st:
+                st['step'] = n
+
     def make_capturable(self, device):
         """Keep the step number on the device so that a captured HIP graph applies the right bias
         corrections on every replay (all parameters of this optimiser step together)."""
-        if getattr(self, 'grad_guard', None) is not None and self.step_dev is not None:
+        if self.grad_guard is not None and self.step_dev is not None:
             # under a gradient guard the device counter is the only one that knows which steps were skipped: it stays where it
             # is (the same memory), and the host-side entries follow it
-            n = int(self.step_dev[0].item())
-            for st in self.state.values():
-                if st:
-                    st['step'] = n
+            self._set_steps(int(self.step_dev[0].item()))
             return
         steps = [int(self.state[p]['step']) for g in self.param_groups for p in g['params'] if p in self.state and self.state[p]]
         if len({tuple(g['betas']) for g in self.param_groups}) != 1:
@@ -72,17 +118,12 @@ class Adam(torch.optim.Optimizer):
             # a second capture (new batch shape): the host-side `step` entries only advance on eager / capture calls, the
             # replays in between advanced the device counter alone — carry on from whichever is further
             n = max(n, int(self.step_dev[0].item()))
-            for st in self.state.values():
-                if st:
-                    st['step'] = n
+            self._set_steps(n)
         self.step_dev = torch.tensor([float(n), 0.0, 0.0], device=device, dtype=torch.float32)
 
     def load_state_dict(self, state_dict):
-        """torch's loader keeps whatever strides the checkpoint's tensors had (`.to(device)` preserves them); the kernels walk the
-        moments as dense arrays through raw pointers, so anything that is not a dense tensor of its own is re-materialised."""
         super().load_state_dict(state_dict)
-        _densify_state(self)
-        if getattr(self, 'grad_guard', None) is not None and self.step_dev is not None:
+        if self.grad_guard is not None and self.step_dev is not None:
             # the device counter is authoritative under a gradient guard: it takes the loaded step number, in place
             steps = [int(st['step']) for st in self.state.values() if st]
             n = max(steps) if steps else 0
@@ -93,24 +134,12 @@ class Adam(torch.optim.Optimizer):
         """Same layout as torch.optim.Adam. Under graph replay the step counter advances on the device only: fold it back
         into the per-parameter `step` entries first, so that a checkpoint resumes with the right bias corrections."""
         if self.step_dev is not None:
-            n = int(self.step_dev[0].item())
-            for st in self.state.values():
-                if st:
-                    st['step'] = n
+            self._set_steps(int(self.step_dev[0].item()))
         return super().state_dict()
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        TF.grad_sink_flush()                  # (no-op unless a backward pass left k-split partial sums pending)
-        if self.weight_hook is not None:
-            self.weight_hook.project_grads()  # spectral norm: dL/dWhat -> dL/dW, and the master W back into the parameters
-        sched = getattr(self, 'lr_sched', None)
-        guard = getattr(self, 'grad_guard', None)
-        if guard is None:
-            self._tick(sched, None)
+    def _collect(self, guard):
         touched, launches = [], []
         for group in self.param_groups:
-            b1, b2 = group['betas']
             by_step = {}                      # tensors that have taken the same number of steps update in one launch
             for p in group['params']:
                 if p.grad is None:
@@ -137,28 +166,15 @@ class Adam(torch.optim.Optimizer):
                         raise ValueError('parameter layout not supported by the fused optimiser: strides %s' % (p.stride(),))
                     by_step.setdefault(st['step'], []).append((p, g, st['exp_avg'], st['exp_avg_sq']))
                 touched.append(p)
-            launches += [(group, step, items) for step, items in by_step.items()]
-        if guard is not None:
-            # --grad_guard / --*_clip: the norm of exactly the gradients the launches below read, the decision, then the ticks
-            # (the step counter stands still on a skipped step; the schedule counts iterations and moves on regardless)
-            every = [it for _, _, items in launches for it in items]
-            if every:
-                guard.measure(TF.adam_jobs(every), len(every), self.grad_scale)
-            else:
-                guard = None                  # nothing to update: nothing to measure, a plain tick
-            self._tick(sched, guard)
-        for group, step, items in launches:
-            b1, b2 = group['betas']
-            TF.adam_step_multi(items, group['lr'], b1, b2, group['eps'], step, self.grad_scale, self.step_dev,
-                               None if sched is None else sched.state, None if guard is None else guard.state)
-        if self.weight_hook is not None:
-            # spectral norm: the parameters hold W / sigma again before they are re-packed — EVERY normalised weight does, also one
-            # that had no gradient in this step (u, v and sigma moved on), so all of them join the re-pack
-            touched = self.weight_hook.refresh(touched)
-        TF.bump_weight_epoch(touched)   # their packed weights are stale ...
-        TF.repack_params(touched)       # ... refresh them in place right away (same addresses for graph replay)
-        return None
+            launches += [(items, group, step) for step, items in by_step.items()]
+        return touched, launches
 
+    _jobs = staticmethod(TF.adam_jobs)
+
+    def _launch(self, sched, guard, items, group, step):
+        b1, b2 = group['betas']
+        TF.adam_step_multi(items, group['lr'], b1, b2, group['eps'], step, self.grad_scale, self.step_dev,
+                           None if sched is None else sched.state, None if guard is None else guard.state)
 
     def _tick(self, sched, guard):
         if self.step_dev is not None:
@@ -168,11 +184,10 @@ class Adam(torch.optim.Optimizer):
                          't2v_adam_tick_guard')
             else:
                 TF.check(TF.lib().t2v_adam_tick(TF._p(self.step_dev), b1, b2, TF._stream()), 't2v_adam_tick')
-        if sched is not None:
-            sched.tick()                      # --lr_decay: this update's factor into device memory, eager and captured alike
+        super()._tick(sched, guard)
 
 
-class SGD(torch.optim.Optimizer):
+class SGD(_FusedOptimizer):
     """`torch.optim.SGD(params, lr, momentum)` on the multi-tensor HIP kernel — the reference's `--sgd` branch
     (train/gan.py:86-89: momentum = beta1). Same `state_dict()` layout (momentum_buffer)."""
 
@@ -180,28 +195,11 @@ class SGD(torch.optim.Optimizer):
         if dampening != 0 or weight_decay != 0 or nesterov:
             raise NotImplementedError('the reference only passes lr and momentum')
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=0, nesterov=False))
-        self.grad_scale = 1.0
-        self.weight_hook = None       # as in Adam
-        self.lr_sched = None          # as in Adam
-        self.grad_guard = None        # as in Adam
 
     def make_capturable(self, device):
         """Nothing step-dependent lives on the host once the momentum buffers exist (they do after the eager warm-up)."""
 
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        _densify_state(self)
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        from ._lib import AdamJob
-        TF.grad_sink_flush()
-        if self.weight_hook is not None:
-            self.weight_hook.project_grads()
-        sched = getattr(self, 'lr_sched', None)
-        guard = getattr(self, 'grad_guard', None)
-        if sched is not None and guard is None:
-            sched.tick()
+    def _collect(self, guard):
         touched, launches = [], []
         for group in self.param_groups:
             mu = float(group['momentum'])
@@ -225,35 +223,26 @@ class SGD(torch.optim.Optimizer):
                     _check_state_layout(self, p, st, ('momentum_buffer',))
                     later.append((p, g, st.get('momentum_buffer')))
                 touched.append(p)
-            launches += [(group, mu, items, is_first) for items, is_first in ((first, 1), (later, 0)) if items]
+            launches += [(items, group, mu, is_first) for items, is_first in ((first, 1), (later, 0)) if items]
+        return touched, launches
 
-        def jobs(items):
-            arr = (AdamJob * len(items))()
-            for a, (p, g, m) in zip(arr, items):
-                a.p, a.g, a.m, a.v, a.n = p.data_ptr(), g.data_ptr(), (m.data_ptr() if m is not None else None), None, p.numel()
-            return arr
+    @staticmethod
+    def _jobs(items):
+        from ._lib import AdamJob
+        arr = (AdamJob * len(items))()
+        for a, (p, g, m) in zip(arr, items):
+            a.p, a.g, a.m, a.v, a.n = p.data_ptr(), g.data_ptr(), (m.data_ptr() if m is not None else None), None, p.numel()
+        return arr
+
+    def _launch(self, sched, guard, items, group, mu, is_first):
+        arr = self._jobs(items)
         if guard is not None:
-            every = [it for _, _, items, _ in launches for it in items]
-            if every:
-                guard.measure(jobs(every), len(every), self.grad_scale)
-            else:
-                guard = None
-            if sched is not None:
-                sched.tick()
-        for group, mu, items, is_first in launches:
-            arr = jobs(items)
-            if guard is not None:
-                TF.check(TF.lib().t2v_sgd_multi_guard(arr, len(items), group['lr'], None if sched is None else TF._p(sched.state),
-                                                      mu, self.grad_scale, is_first, TF._p(guard.state), TF._stream()),
-                         't2v_sgd_multi_guard')
-            elif sched is not None:
-                TF.check(TF.lib().t2v_sgd_multi_sched(arr, len(items), group['lr'], TF._p(sched.state), mu, self.grad_scale,
-                                                      is_first, TF._stream()), 't2v_sgd_multi_sched')
-            else:
-                TF.check(TF.lib().t2v_sgd_multi(arr, len(items), group['lr'], mu, self.grad_scale, is_first, TF._stream()),
-                         't2v_sgd_multi')
-        if self.weight_hook is not None:
-            touched = self.weight_hook.refresh(touched)
-        TF.bump_weight_epoch(touched)
-        TF.repack_params(touched)
-        return None
+            TF.check(TF.lib().t2v_sgd_multi_guard(arr, len(items), group['lr'], None if sched is None else TF._p(sched.state),
+                                                  mu, self.grad_scale, is_first, TF._p(guard.state), TF._stream()),
+                     't2v_sgd_multi_guard')
+        elif sched is not None:
+            TF.check(TF.lib().t2v_sgd_multi_sched(arr, len(items), group['lr'], TF._p(sched.state), mu, self.grad_scale,
+                                                  is_first, TF._stream()), 't2v_sgd_multi_sched')
+        else:
+            TF.check(TF.lib().t2v_sgd_multi(arr, len(items), group['lr'], mu, self.grad_scale, is_first, TF._stream()),
+                     't2v_sgd_multi')

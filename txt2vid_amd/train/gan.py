@@ -1,6 +1,7 @@
 """CLI entry of the TGANv2 hot path — flag-for-flag txt2vid/train/gan.py:28-221 (+ trainer.py:15-42), so
 `scripts/run_tganv2*.sh` / `config/*.json` drive this build. One process per GPU: launched under
 `torch.distributed.run` it trains data-parallel over RCCL (the reference's `--ngpu` was never read).
+The opt-in features are built in `main()` in a load-bearing order, from the flags and the checkpoint's extra keys.
 
     python -m txt2vid_amd.train.gan --data config/synth.json --G txt2vid.models.tganv2.gen.MultiScaleGen ...
 """
@@ -18,7 +19,7 @@ from ..util.log import status
 from ..util.pick import load
 from ..util.reflection import create_object
 from ..util.torch.init import init
-from .setup import setup
+from .setup import setup, set_rng_state
 
 
 def _model(spec, args, kind='D', **kw):
@@ -34,15 +35,14 @@ def _model(spec, args, kind='D', **kw):
 
 
 def main(args):
-    from ..gan.spectral import check_flags, check_checkpoint
+    from ..gan import ada, grad_guard, lr_sched
+    from ..gan.ema import GenAverage
+    from ..gan.spectral import check_flags, check_checkpoint, SpectralNorm, attach
+    # the flags' rules are checked before a process group forms (a data-parallel start with --D_ada is refused here)
     check_flags(args)
-    from ..gan.ada import check_args, AdaState
-    # --D_aug_p / --D_ada: the rules are checked before a process group forms (a data-parallel start with --D_ada is refused)
-    check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
-    from ..gan import lr_sched
-    lr_sched.check_args(args)            # --lr_decay: likewise refused here, before a process group forms
-    from ..gan import grad_guard
-    grad_guard.check_args(args)          # --grad_guard / --D_clip / --G_clip: likewise
+    ada.check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
+    lr_sched.check_args(args)
+    grad_guard.check_args(args)
     from .. import dist as tdist
     rank, world = tdist.init_from_env('nccl')
     from ..util.misc import limit_host_threads
@@ -97,94 +97,78 @@ def main(args):
     else:
         optD = Adam(D_params, lr=args.D_lr, betas=(args.D_beta1, args.D_beta2))
         optG = Adam(G_params, lr=args.G_lr, betas=(args.G_beta1, args.G_beta2))
-    resumed_rng, resumed_iter, resumed_ema, resumed_sn, resumed_lr, resumed_guard = None, 0, None, None, None, None
+    ck = {}      # the checkpoint's entries outside the reference's layout, for the opt-in features below (their order: DESIGN §22)
     gan = CondGan(gen=gen, discrims=discrims, cond_encoder=txt_encoder, discrim_names=args.D_names,
                   discrim_lambdas=args.D_lambdas, gp_scale=float(world))
     if args.D_ada is not None:
-        # adaptive strength of --D_aug (not in the reference): the controller's state lives on the device and in the checkpoint
-        # (key 'ada'); a file without the key starts from --D_aug_p
-        gan.ada = AdaState(args.D_ada, args.D_ada_interval, args.D_ada_kclips, args.D_aug_p, device)
+        # (in front of load_from_dict, which loads its state: a file without the key 'ada' starts from --D_aug_p)
+        gan.ada = ada.AdaState(args.D_ada, args.D_ada_interval, args.D_ada_kclips, args.D_aug_p, device)
         status('Adaptive augmentation strength: target %g, update every %d D steps, %g kclips, initial p %g (defaults are the '
                "paper's values for images, untuned for video)" % (args.D_ada, args.D_ada_interval, args.D_ada_kclips, args.D_aug_p))
     if args.weights is not None:
         to_load = torch.load(args.weights, map_location=device, weights_only=False)
-        resumed_sn = check_checkpoint(to_load, args.D_sn, args.weights)
+        check_checkpoint(to_load, args.D_sn, args.weights)
         gan.load_from_dict(to_load)
         if 'optD' in to_load:
             optD.load_state_dict(to_load['optD'])
         if 'optG' in to_load:
             optG.load_state_dict(to_load['optG'])
-        resumed_rng, resumed_iter = to_load.get('rng_state'), int(to_load.get('iteration', 0))
-        if 'gen_ema' in to_load and args.G_ema > 0:
-            resumed_ema = (to_load['gen_ema'], to_load.get('gen_ema_updates', 0))
-        resumed_lr = to_load.get('lr_sched')
-        resumed_guard = to_load.get('grad_guard')
+        ck = {k: v for k, v in to_load.items() if k in ('rng_state', 'iteration', 'gen_ema_updates', 'discrim_sn', 'lr_sched',
+                                                         'grad_guard') or (k == 'gen_ema' and args.G_ema > 0)}
         del to_load
     if gan.ada is not None:
         st = gan.ada.ada.tolist()
         status('Augmentation probability p = %r; window: sign sum %g over %g pairs in %g D steps' % (st[0], st[1], st[2], st[3]))
     if args.lr_decay != 'none':
-        # learning-rate decay inside the replayed graph (not in the reference): two floats of device state per optimiser, saved
-        # under the checkpoint's key 'lr_sched'. Every rank ticks identical state, so data-parallel runs need no exchange
+        # (behind the optimisers' own state. Every rank ticks identical state: no exchange)
         sched = lr_sched.LrSchedule(args.lr_decay, args.lr_decay_iters, args.lr_decay_start, args.lr_final, args.discrim_steps,
                                     args.gen_steps, device).attach(optD, optG)
-        for note in sched.load_state_dict(resumed_lr, resumed_iter):
+        for note in sched.load_state_dict(ck.get('lr_sched'), int(ck.get('iteration', 0))):
             status('Learning-rate schedule: ' + note)
         k = sched.counters()
         status('Learning-rate schedule: %s from iteration %d to %d, final fraction %g; D at update %d, G at update %d' % (
             args.lr_decay, args.lr_decay_start, args.lr_decay_iters, args.lr_final, k['D'], k['G']))
-    elif resumed_lr is not None:
-        status('the checkpoint holds a learning-rate schedule state (%s); without --lr_decay it is ignored' % (resumed_lr,))
+    elif 'lr_sched' in ck:
+        status('the checkpoint holds a learning-rate schedule state (%s); without --lr_decay it is ignored' % (ck['lr_sched'],))
     if grad_guard.enabled(args):
-        # gradient clipping and the non-finite guard inside the replayed graph (not in the reference): eight floats of device state
-        # per optimiser, the counts saved under the checkpoint's key 'grad_guard'. Gradients are identical on every rank after the
-        # exchange and the reduction is deterministic, so every rank takes the same decision: no exchange of its own
+        # (likewise. Every rank sees the same gradients and takes the same decision: no exchange)
         guard = grad_guard.GradGuard(args.D_clip, args.G_clip, device).attach(optD, optG)
         if args.weights is not None:
-            for note in guard.load_state_dict(resumed_guard):
+            for note in guard.load_state_dict(ck.get('grad_guard')):
                 status('Gradient guard: ' + note)
         k = guard.counters()
         status('Gradient guard: D clip %s, G clip %s, non-finite steps are skipped; D %d steps (%d skipped, %d clipped), '
                'G %d steps (%d skipped, %d clipped) so far' % (
                    'off' if args.D_clip is None else '%g' % args.D_clip, 'off' if args.G_clip is None else '%g' % args.G_clip,
                    k['D']['steps'], k['D']['skipped'], k['D']['clipped'], k['G']['steps'], k['G']['skipped'], k['G']['clipped']))
-    elif resumed_guard is not None:
+    elif 'grad_guard' in ck:
         status('the checkpoint holds gradient-guard counts (%s); without --grad_guard / --D_clip / --G_clip the key is ignored'
-               % (resumed_guard,))
+               % (ck['grad_guard'],))
     if world > 1:
-        # replicas bit-identical before the first step (whatever each rank's init / checkpoint read produced), then per-rank
-        # generators for everything drawn per iteration (z, sub-sample phases, GP alphas, caption permutations)
+        # replicas bit-identical before the first step, then per-rank generators for everything drawn per iteration
         from .. import functional as TF
         tdist.sync_replicas([gen] + list(discrims) + [txt_encoder])
         TF.bump_weight_epoch()
         import random
         import numpy as np
         for seeder in (random.seed, np.random.seed, torch.manual_seed):
-            seeder(seed + rank + 1000003 * resumed_iter)     # (a resumed run does not replay the first run's draws)
+            seeder(seed + rank + 1000003 * int(ck.get('iteration', 0)))     # (a resumed run does not replay the first run's draws)
     if args.G_ema > 0:
-        # moving average of the generator's weights (not in the reference): built from the loaded / initialised and synchronised
-        # weights; every rank then applies the same update to identical replicas, so the averages need no exchange
-        from ..gan.ema import GenAverage
+        # (from the loaded / initialised and synchronised weights, identical on every rank: no exchange)
         gan.gen_ema = GenAverage(gen, args.G_ema, start=args.G_ema_start)
-        if resumed_ema is not None:
-            gan.gen_ema.load_state_dict(*resumed_ema)
+        if 'gen_ema' in ck:
+            gan.gen_ema.load_state_dict(ck['gen_ema'], ck.get('gen_ema_updates', 0))
         status('Averaged generator: decay %g after %d updates (%d updates so far)' % (args.G_ema, args.G_ema_start,
                                                                                      gan.gen_ema.updates))
     if args.D_sn:
-        # spectral normalisation of the discriminators (not in the reference), built from the loaded / initialised and synchronised
-        # weights: a checkpoint with its state continues bit for bit, any other has its weights taken as W. u is drawn from a
-        # generator of its own seeded with the run's seed (the same on every rank), so the replicas stay identical without an
-        # exchange and no draw of the training loop moves
-        from ..gan.spectral import SpectralNorm, attach
-        attach(gan, optD, SpectralNorm(discrims, seed=seed, state=resumed_sn))
+        # (likewise. A checkpoint with its state continues bit for bit; u comes from a generator of its own)
+        attach(gan, optD, SpectralNorm(discrims, seed=seed, state=ck.get('discrim_sn')))
         status('Spectral normalisation of %d discriminator weights (%s)' % (
-            len(gan.discrim_sn.params), 'state from the checkpoint' if resumed_sn is not None else '%d initial power iterations'
+            len(gan.discrim_sn.params), 'state from the checkpoint' if 'discrim_sn' in ck else '%d initial power iterations'
             % gan.discrim_sn.n_init))
-    if resumed_rng is not None and rank == 0:
-        # checkpoints written by this build carry the writer's (rank 0's) generator states: the resumed run continues the draw
-        # sequence where the saved one stopped (reference-written files have no such key and start from --seed)
-        from .setup import set_rng_state
-        set_rng_state(resumed_rng)
+    if ck.get('rng_state') is not None and rank == 0:
+        # the writer's (rank 0's) generator states: the run continues the saved draw sequence (reference files have no such key)
+        set_rng_state(ck['rng_state'])
     transform = data.default_transform(frame_size=[args.frame_sizes[-1]], num_channels=args.num_channels)
     dset = create_object(args.data, vocab=vocab, anno=args.anno, transform=transform, size=args.frame_sizes[-1],
                          channels=args.num_channels, seed=(args.seed or 0) + rank)
