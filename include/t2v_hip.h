@@ -723,6 +723,28 @@ int t2v_diffaug_gated_fwd(const t2v_aug_member* members, const float* const* gat
 int t2v_diffaug_gated_bwd(const t2v_aug_member* members, const float* const* gates, int n, const float* p, void* stream);
 int t2v_ada_update(float* ada, const t2v_ada_level* levels, int n, float target, float step, int interval, void* stream);
 
+/* ---- LeCam regularisation of the discriminator (Tseng et al. 2021; opt-in, --D_lecam) -------------------------------
+ * lecam float32[20] (device) = { n, R_last, gate_last, L, alpha_R[0..7], alpha_F[0..7] }: n counts the D steps seen (exact up to
+ * 2^24), the anchors alpha_R[l] / alpha_F[l] are moving averages of the unconditional logits of level l on real / generated clips.
+ * t2v_lecam_fwd, ONE workgroup, with n and the anchors as they stood before the launch:
+ *   gate = n >= max(start, 1);   R = 1/L sum_l [ mean_i (real[l][i] - alpha_F[l])^2 + mean_i (fake[l][i] - alpha_R[l])^2 ];
+ *   out[0] = gate ? R : 0;  saved float32[2L + 1] = { alpha_R[0..L-1], alpha_F[0..L-1], gate } as USED;  then
+ *   alpha <- mean (n == 0) or decay * alpha + (1 - decay) * mean;  n <- n + 1;  R_last = R (ungated), gate_last = gate, lecam[3] = L.
+ * The sums run in a fixed order (per-thread strided partials, wave reduction, four waves through LDS), without atomics: the same
+ * bits run to run. Their combination is done in double and rounded once per stored float.
+ * t2v_lecam_bwd, pointwise over all levels in one launch, g the incoming gradient of out (one float in DEVICE memory):
+ *   d_real[l][i] = gate * g * 2 (real[l][i] - alpha_F[l]) / (L * count_l),   d_fake[l][i] likewise against alpha_R[l],
+ * with gate and anchors from `saved` (the anchors are constants of differentiation); exact zeros with the gate off; a NULL
+ * d_real / d_fake is a side that needs no gradient (no launch when every one is NULL).
+ * `levels` are HOST arrays with device pointers inside. T2V_EINVAL, before any launch, on a NULL state / levels / saved / out / g,
+ * n outside 1..T2V_MAX_GROUPS, count < 1, a NULL logit pointer, a decay outside [0, 1) or not finite, start < 0. Neither
+ * allocates nor synchronises; both can be captured. */
+typedef struct t2v_lecam_grad {
+    const float* real; const float* fake; float* d_real; float* d_fake; int32_t count; int32_t reserved;
+} t2v_lecam_grad;
+int t2v_lecam_fwd(float* lecam, const t2v_ada_level* levels, int n, float decay, int start, float* saved, float* out, void* stream);
+int t2v_lecam_bwd(const t2v_lecam_grad* levels, int n, const float* saved, const float* g, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

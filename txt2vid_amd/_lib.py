@@ -102,6 +102,12 @@ class AdaLevel(C.Structure):
     _fields_ = [('real', C.c_void_p), ('fake', C.c_void_p), ('count', C.c_int32), ('reserved', C.c_int32)]
 
 
+class LecamGrad(C.Structure):
+    """t2v_lecam_grad (include/t2v_hip.h)."""
+    _fields_ = [('real', C.c_void_p), ('fake', C.c_void_p), ('d_real', C.c_void_p), ('d_fake', C.c_void_p), ('count', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 MAX_GROUPS = 8
 _P = C.c_void_p
 _I = C.c_int
@@ -251,6 +257,8 @@ SIGNATURES = {
     't2v_diffaug_gated_fwd': [_P, _P, _I, _P, _P],
     't2v_diffaug_gated_bwd': [_P, _P, _I, _P, _P],
     't2v_ada_update': [_P, _P, _I, _F, _F, _I, _P],
+    't2v_lecam_fwd': [_P, _P, _I, _F, _I, _P, _P, _P],
+    't2v_lecam_bwd': [_P, _I, _P, _P, _P],
     't2v_prof_begin': [_I],
     't2v_prof_end': [C.POINTER(C.c_double), _I],
     't2v_version': [],

@@ -321,3 +321,121 @@ extern "C" int t2v_ada_update(float* ada, const t2v_ada_level* levels, int n, fl
     T2V_LAUNCH(ada_update_k, dim3(1), dim3(256), 0, S_(st), ada, tb, (float)pairs, target, step, (float)interval);
     return launch_status();
 }
+
+// ---- LeCam regularisation of the discriminator (Tseng et al. 2021; opt-in through --D_lecam) ----------------------
+// lecam float32[20] = {n, R_last, gate_last, L, alpha_R[0..7], alpha_F[0..7]}: the anchors are moving averages of D's own
+// unconditional logits on real / generated clips, per pyramid level. The forward is ONE workgroup: per level the four sums
+// (sum u_r, sum u_f, sum (u_r - alpha_F)^2, sum (u_f - alpha_R)^2) as per-thread strided partials, a 64-lane wave reduction and
+// the four waves through LDS — a fixed order, no atomics — then thread 0 combines them in double (one rounding per stored
+// float), stores the anchors IT USED and the gate into `saved` for the backward, moves the anchors and increments n.
+#define LECAM_N 20
+#define LECAM_AR 4
+#define LECAM_AF 12
+
+struct LecamBatch {
+    t2v_ada_level l[T2V_MAX_GROUPS];
+    int n;
+};
+
+struct LecamGradBatch {
+    t2v_lecam_grad l[T2V_MAX_GROUPS];
+    int n;
+};
+
+__global__ __launch_bounds__(256) void lecam_fwd_k(float* __restrict__ state, LecamBatch tb, float decay, float start,
+                                                   float* __restrict__ saved, float* __restrict__ out) {
+    __shared__ float red[4][4];
+    __shared__ float sums[T2V_MAX_GROUPS][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int g = 0; g < tb.n; ++g) {
+        const float* __restrict__ r = tb.l[g].real;
+        const float* __restrict__ f = tb.l[g].fake;
+        const float aR = state[LECAM_AR + g], aF = state[LECAM_AF + g];      // (thread 0 writes them behind the last barrier)
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        for (long j = threadIdx.x; j < tb.l[g].count; j += 256) {
+            const float a = r[j], b = f[j], da = a - aF, db = b - aR;
+            v[0] += a;
+            v[1] += b;
+            v[2] += da * da;
+            v[3] += db * db;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = wave_sum(v[k]);
+        __syncthreads();
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) red[wave][k] = v[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < 4) sums[g][threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const float n = state[0];
+    const float gate = n >= start ? 1.f : 0.f;                                // start >= 1: the first step has no anchors yet
+    const double d = (double)decay;
+    double R = 0.0;
+    for (int g = 0; g < tb.n; ++g) {
+        const double cnt = (double)tb.l[g].count;
+        const float aR = state[LECAM_AR + g], aF = state[LECAM_AF + g];
+        R += ((double)sums[g][2] + (double)sums[g][3]) / cnt;
+        saved[g] = aR;
+        saved[tb.n + g] = aF;
+        const double mr = (double)sums[g][0] / cnt, mf = (double)sums[g][1] / cnt;
+        state[LECAM_AR + g] = n == 0.f ? (float)mr : (float)(d * (double)aR + (1.0 - d) * mr);
+        state[LECAM_AF + g] = n == 0.f ? (float)mf : (float)(d * (double)aF + (1.0 - d) * mf);
+    }
+    const float Rf = (float)(R / (double)tb.n);
+    saved[2 * tb.n] = gate;
+    out[0] = gate != 0.f ? Rf : 0.f;
+    state[0] = n + 1.f;
+    state[1] = Rf;
+    state[2] = gate;
+    state[3] = (float)tb.n;
+}
+
+// blockIdx.y: the level; its elements grid-strided over blockIdx.x. dL/du_r = gate * g * 2 (u_r - alpha_F) / (L * count), the
+// anchors being constants of differentiation; exact zeros with the gate off.
+__global__ __launch_bounds__(256) void lecam_bwd_k(LecamGradBatch tb, const float* __restrict__ saved, const float* __restrict__ gp) {
+    const t2v_lecam_grad l = tb.l[blockIdx.y];
+    const float aR = saved[blockIdx.y], aF = saved[tb.n + blockIdx.y], gate = saved[2 * tb.n];
+    const float c = (gp[0] * 2.f) / ((float)tb.n * (float)l.count);
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < l.count; j += (long)gridDim.x * 256) {
+        if (l.d_real) l.d_real[j] = gate != 0.f ? c * (l.real[j] - aF) : 0.f;
+        if (l.d_fake) l.d_fake[j] = gate != 0.f ? c * (l.fake[j] - aR) : 0.f;
+    }
+}
+
+extern "C" int t2v_lecam_fwd(float* state, const t2v_ada_level* levels, int n, float decay, int start, float* saved, float* out,
+                             void* st) {
+    if (!state || !levels || !saved || !out || n < 1 || n > T2V_MAX_GROUPS || start < 0) return T2V_EINVAL;
+    if (!(decay >= 0.f) || !(decay < 1.f)) return T2V_EINVAL;                 // outside [0, 1), or NaN
+    LecamBatch tb;
+    for (int g = 0; g < T2V_MAX_GROUPS; ++g) {
+        tb.l[g] = g < n ? levels[g] : t2v_ada_level{};
+        if (g < n && (!levels[g].real || !levels[g].fake || levels[g].count < 1)) return T2V_EINVAL;
+    }
+    tb.n = n;
+    T2V_LAUNCH(lecam_fwd_k, dim3(1), dim3(256), 0, S_(st), state, tb, decay, (float)(start < 1 ? 1 : start), saved, out);
+    return launch_status();
+}
+
+extern "C" int t2v_lecam_bwd(const t2v_lecam_grad* levels, int n, const float* saved, const float* g, void* st) {
+    if (!levels || !saved || !g || n < 1 || n > T2V_MAX_GROUPS) return T2V_EINVAL;
+    LecamGradBatch tb;
+    int most = 0;
+    bool any = false;
+    for (int k = 0; k < T2V_MAX_GROUPS; ++k) {
+        tb.l[k] = k < n ? levels[k] : t2v_lecam_grad{};
+        if (k >= n) continue;
+        if (!levels[k].real || !levels[k].fake || levels[k].count < 1) return T2V_EINVAL;
+        most = levels[k].count > most ? levels[k].count : most;
+        any = any || levels[k].d_real || levels[k].d_fake;
+    }
+    if (!any) return T2V_OK;                                                  // no side needs a gradient: nothing to launch
+    tb.n = n;
+    long bx = ((long)most + 255) / 256;
+    bx = bx > 1024 ? 1024 : bx;
+    T2V_LAUNCH(lecam_bwd_k, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, S_(st), tb, saved, g);
+    return launch_status();
+}

@@ -39,12 +39,25 @@ class CondGan(object):
         self.gen_ema = gen_ema            # gan.ema.GenAverage of `gen` (--G_ema, not in the reference), or None
         self.discrim_sn = None            # gan.spectral.SpectralNorm of `discrims` (--D_sn, not in the reference), or None
         self.ada = None                   # gan.ada.AdaState, the controller of the augmentation's p (--D_ada, not in the reference), or None
+        self.lecam = None                 # gan.lecam.LeCamState, the anchors of the LeCam term (--D_lecam, not in the reference), or None
 
     def _observe(self, discrim, u_r, u_f):
         """--D_ada: the unconditional logits of the `lu` term of a D step feed the controller (the first discriminator's alone):
         one launch behind this D forward."""
         if self.ada is not None and discrim is self.discrims[0]:
             self.ada.observe(list(u_r), list(u_f))
+
+    def _lecam(self, discrim, u_r, u_f):
+        """--D_lecam: the unconditional logits of a D step (the first discriminator's alone) feed the loss AND the
+        regulariser. Returns (u_r, u_f, operands): the logits for the loss, and what the D loss gains as ([gate * R], [lambda]),
+        operands and weights for the `scalar_sum` that adds the gradient penalty; or the logits as they are and ([], []).
+        One grouped fork over the 2L tensors, so that ONE launch sums the two gradients of all of them (not the engine, with an
+        ATen add per tensor); one launch for the term, which also moves the anchors."""
+        if self.lecam is None or discrim is not self.discrims[0]:
+            return u_r, u_f, ([], [])
+        n = len(u_r)
+        mine, its = TF.fork_group(list(u_r) + list(u_f))
+        return mine[:n], mine[n:], ([self.lecam.term(its[:n], its[n:])], [self.lecam.lam])
 
     def _discrim_weighted_sum(self, losses, kl=None, kl_coeff=0.0):
         """cond_gan.py:26-31: mean over discriminators, or lambda-weighted sum. `kl`: the generator's conditioning-augmentation
@@ -63,6 +76,7 @@ class CondGan(object):
         if loss is not None and real is not None and fake is not None and _fusable(discrim, real, fake):
             return self._discrim_forward_fused(discrim, real, fake, real_cond, fake_cond, loss, gp_lambda)
         fake_pred = real_pred = l = None
+        reg = ([], [])
         if real_cond is not None and fake_cond is not None:
             real_cc = discrim(x=real, cond=real_cond, xbar=None)
             real_pred = real_cc
@@ -74,7 +88,8 @@ class CondGan(object):
                            for i in range(len(real))] if hasattr(discrim, 'sub_discrims') else \
                     discrim(x=real, cond=fake_cond, xbar=None)
                 fake_cc = discrim(x=fake, cond=real_cond, xbar=None)
-                lu = TF.scalar_mean([loss(fake=f[0], real=r[0]) for f, r in zip(fake_cc, real_cc)])
+                u_r, u_f, reg = self._lecam(discrim, [r[0] for r in real_cc], [f[0] for f in fake_cc])
+                lu = TF.scalar_mean([loss(fake=f, real=r) for f, r in zip(u_f, u_r)])
                 self._observe(discrim, [r[0] for r in real_cc], [f[0] for f in fake_cc])
                 l1 = TF.scalar_mean([loss(fake=f[1], real=r[1]) for f, r in zip(fake_cc, real_cc)])
                 l2 = TF.scalar_mean([loss(fake=f[1], real=r[1]) for f, r in zip(real_ic, real_cc)])
@@ -86,12 +101,15 @@ class CondGan(object):
             if fake is not None:
                 fake_pred = [f[0] for f in discrim(x=fake, cond=None, xbar=None)]
             if loss is not None and fake_pred is not None and real_pred is not None:
-                l = TF.scalar_mean([loss(fake=f, real=r) for f, r in zip(fake_pred, real_pred)])
+                u_r, u_f, reg = self._lecam(discrim, real_pred, fake_pred)
+                l = TF.scalar_mean([loss(fake=f, real=r) for f, r in zip(u_f, u_r)])
                 self._observe(discrim, real_pred, fake_pred)
         if l is not None and gp_lambda > 0:
             gp = gradient_penalty(discrim, real_x=real, fake_x=fake, real_cond=real_cond, fake_cond=fake_cond,
                                   scale=self.gp_scale)
-            l = TF.scalar_sum([l, gp], weights=[1.0, gp_lambda])
+            l = TF.scalar_sum([l, gp] + reg[0], weights=[1.0, gp_lambda] + reg[1])
+        elif reg[0]:
+            l = TF.scalar_sum([l] + reg[0], weights=[1.0] + reg[1])
         return l, fake_pred, real_pred
 
     def _discrim_forward_fused(self, discrim, real, fake, real_cond, fake_cond, loss, gp_lambda):
@@ -127,6 +145,8 @@ class CondGan(object):
         b = [r.size(0) for r in real]
         u_r, u_f = TF.split_rows_group([o[0] for o in both], b)
         self._observe(discrim, u_r, u_f)
+        pred_r, pred_f = u_r, u_f
+        u_r, u_f, reg = self._lecam(discrim, u_r, u_f)
         if cond:
             c_r, c_f = TF.split_rows_group([o[1] for o in both], b)
             # D(real, mismatched captions): second head on the real half's trunk features
@@ -142,11 +162,11 @@ class CondGan(object):
             l1 = _mean_over_levels(loss, c_f, c_r1)
             l2 = _mean_over_levels(loss, c_ic, c_r2)
             l = TF.scalar_sum([lu, l1, l2], weights=[0.5, 0.25, 0.25])
-            real_pred = [(u_r[i], c_r[i], TF.head_rows(both[i][2], b[i])) for i in range(n)]
+            real_pred = [(pred_r[i], c_r[i], TF.head_rows(both[i][2], b[i])) for i in range(n)]
             fake_pred = None
         else:
             l = _mean_over_levels(loss, u_f, u_r)
-            real_pred, fake_pred = list(u_r), list(u_f)
+            real_pred, fake_pred = list(pred_r), list(pred_f)
         if gp_lambda > 0:
             outs = []
             for u, c, _ in gp_res:
@@ -163,7 +183,9 @@ class CondGan(object):
                 gp = TF.scalar_sum([TF.dot_group(ga, gb)], weights=[self.gp_scale])
             else:
                 gp = TF.scalar_sum([TF.vec_sum(TF.row_sqnorm(g), self.gp_scale) for g in gs])
-            l = TF.scalar_sum([l, gp], weights=[1.0, gp_lambda])
+            l = TF.scalar_sum([l, gp] + reg[0], weights=[1.0, gp_lambda] + reg[1])
+        elif reg[0]:
+            l = TF.scalar_sum([l] + reg[0], weights=[1.0] + reg[1])
         return l, fake_pred, real_pred
 
     def gen_step_fused(self, fake=None, real=None, cond=None, loss=None, draw_perm=True, kl=None, kl_coeff=0.0):
@@ -284,6 +306,8 @@ class CondGan(object):
             res['discrim_sn'] = self.discrim_sn.state_dict()
         if self.ada is not None:
             res['ada'] = self.ada.state_dict()
+        if self.lecam is not None:
+            res['lecam'] = self.lecam.state_dict()
         return res
 
     def load_from_dict(self, to_load):
@@ -303,6 +327,9 @@ class CondGan(object):
             # a file without the key (written without --D_ada, or by the reference) starts from p0 with an empty window; a file with
             # the key loaded into a run without a controller ignores it
             self.ada.load_state_dict(to_load.get('ada'))
+        if self.lecam is not None:
+            # likewise: a file without the key starts with n = 0 and no anchors; a key without the feature is ignored
+            self.lecam.load_state_dict(to_load.get('lecam'))
 
 
 def _can_batch(real, fake):

@@ -67,8 +67,8 @@ def _positive(kind, flag):
 
 def add_params_to_parser(parser):
     """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema,
-    --G_ema_start, --D_aug, --D_aug_p, --D_ada, --D_ada_interval, --D_ada_kclips, --D_sn, --lr_decay, --lr_decay_iters,
-    --lr_decay_start, --lr_final, --grad_guard, --D_clip and --G_clip are new."""
+    --G_ema_start, --D_aug, --D_aug_p, --D_ada, --D_ada_interval, --D_ada_kclips, --D_lecam, --D_lecam_decay, --D_lecam_start,
+    --D_sn, --lr_decay, --lr_decay_iters, --lr_decay_start, --lr_final, --grad_guard, --D_clip and --G_clip are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
     parser.add_argument('--log_period', type=int, default=20)
@@ -109,6 +109,16 @@ def add_params_to_parser(parser):
     parser.add_argument('--D_ada_kclips', type=_positive(float, '--D_ada_kclips'), default=500.0,
                         help='(new) thousands of clips in which the probability can move from 0 to 1 '
                              "(the paper's value for images; untuned here)")
+    parser.add_argument('--D_lecam', type=_positive(float, '--D_lecam'), default=None, metavar='LAMBDA',
+                        help='(new) LeCam regularisation (Tseng et al. 2021): add LAMBDA > 0 times the mean squared distance of '
+                             "the discriminator's unconditional logits on real / generated clips to a moving average of its "
+                             'logits on generated / real clips. One discriminator, single-GPU runs only. The paper uses 0.3 with '
+                             'hinge-scale logits on images: nobody has tuned it for video or for the relativistic loss')
+    parser.add_argument('--D_lecam_decay', type=float, default=None, metavar='DECAY',
+                        help='(new) decay of the moving averages of --D_lecam, in [0, 1) (default 0.99)')
+    parser.add_argument('--D_lecam_start', type=int, default=None, metavar='N',
+                        help='(new) discriminator steps before the term of --D_lecam counts; the averages move from the first '
+                             'step (default 0)')
     parser.add_argument('--D_sn', action='store_true', default=False,
                         help='(new) spectral normalisation of every Conv3d / Linear weight of the discriminators: one power '
                              'iteration after each discriminator update')

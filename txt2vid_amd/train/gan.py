@@ -35,12 +35,13 @@ def _model(spec, args, kind='D', **kw):
 
 
 def main(args):
-    from ..gan import ada, grad_guard, lr_sched
+    from ..gan import ada, grad_guard, lecam, lr_sched
     from ..gan.ema import GenAverage
     from ..gan.spectral import check_flags, check_checkpoint, SpectralNorm, attach
     # the flags' rules are checked before a process group forms (a data-parallel start with --D_ada is refused here)
     check_flags(args)
     ada.check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
+    lecam.check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
     lr_sched.check_args(args)
     grad_guard.check_args(args)
     from .. import dist as tdist
@@ -105,6 +106,11 @@ def main(args):
         gan.ada = ada.AdaState(args.D_ada, args.D_ada_interval, args.D_ada_kclips, args.D_aug_p, device)
         status('Adaptive augmentation strength: target %g, update every %d D steps, %g kclips, initial p %g (defaults are the '
                "paper's values for images, untuned for video)" % (args.D_ada, args.D_ada_interval, args.D_ada_kclips, args.D_aug_p))
+    if args.D_lecam is not None:
+        # (likewise in front of load_from_dict: a file without the key 'lecam' starts with no anchors)
+        gan.lecam = lecam.LeCamState(args.D_lecam, args.D_lecam_decay, args.D_lecam_start, device)
+        status('LeCam regularisation of the discriminator: weight %g, anchor decay %g, from D step %d (0.3 is the paper\'s value for '
+               'images, untuned for video)' % (args.D_lecam, args.D_lecam_decay, args.D_lecam_start))
     if args.weights is not None:
         to_load = torch.load(args.weights, map_location=device, weights_only=False)
         check_checkpoint(to_load, args.D_sn, args.weights)
@@ -119,6 +125,11 @@ def main(args):
     if gan.ada is not None:
         st = gan.ada.ada.tolist()
         status('Augmentation probability p = %r; window: sign sum %g over %g pairs in %g D steps' % (st[0], st[1], st[2], st[3]))
+    if gan.lecam is not None:
+        st = gan.lecam.lecam.tolist()
+        n_lv = int(st[3])
+        status('LeCam state: %d D steps seen, last R %r (gate %d); anchors real %r, fake %r' % (
+            int(st[0]), st[1], int(st[2]), st[lecam.A_R:lecam.A_R + n_lv], st[lecam.A_F:lecam.A_F + n_lv]))
     if args.lr_decay != 'none':
         # (behind the optimisers' own state. Every rank ticks identical state: no exchange)
         sched = lr_sched.LrSchedule(args.lr_decay, args.lr_decay_iters, args.lr_decay_start, args.lr_final, args.discrim_steps,
