@@ -288,6 +288,47 @@ int t2v_bn_train_bwd_add(const float* gy, const float* x, const float* y, const 
 int t2v_bn_eval(const float* x, const float* rm, const float* rv, const float* gamma, const float* beta,
                 float* y, int N, int C, int64_t S, float eps, int relu, void* stream);
 
+/* ---- conditional BatchNorm2d of the text-conditioned generator (opt-in, MultiScaleGen(cond_bn=True); not in the reference) ----
+ * x is [N,C,H,W] with frames merged into the batch. Row n belongs to level sample j = n / T and reads base row j * s of the
+ * modulation table `tab` [R, ld] (s = 2^level in training mode, where Subsample keeps samples ::2; 1 in eval mode); the site
+ * owns columns off .. off + 2C, laid out [dgamma (C) | dbeta (C)]:
+ *     xhat = (x - mean_c) * istd_c        batch statistics over all rows, running statistics and step counter as t2v_bn_train_fwd
+ *     y    = xhat * (gamma_c + tab[j*s, off + c]) + (beta_c + tab[j*s, off + C + c])      then [ReLU], [x2 up-sampling]
+ * The statistics do not depend on the affine: stats, running statistics and counter equal t2v_bn_train_fwd's on the same x,
+ * bit for bit (the same statistics kernel and merge). Eval mode: the running statistics and the same per-sample affine.
+ * Backward, with g' = dL/dy behind the ReLU mask / up-sampling adjoint, M = N*H*W and Gamma[n,c] = gamma_c + tab[j*s, off + c]:
+ *     sb[n,c] = sum_hw g'   sg[n,c] = sum_hw g' * xhat   dbeta_c = sum_n sb   dgamma_c = sum_n sg
+ *     A_c = sum_n Gamma sb  B_c = sum_n Gamma sg         dx = istd_c * (Gamma * g' - A_c / M - xhat * B_c / M) [+ gx_add]
+ * and gtab [R, ld] (same layout as tab) receives, in the site's 2C columns of EVERY one of its R rows, the sums of sg / sb
+ * over the T rows of the sample that reads that table row, or an exact zero where the level holds no such sample; columns
+ * outside off .. off + 2C are not touched. So the 16 sites of a generator fill one buffer that needs no clearing.
+ * Two launches each way (forward: statistics, merge + apply; backward: per-row sums, merge + apply): the per-row sums take
+ * the place of the plain site's per-slice sums, so the backward adds no launch. Fixed-order reductions (wave64 shuffles,
+ * then LDS), no atomics: the same bits run to run. fp32 only. First order only.
+ * Every entry point returns T2V_EINVAL before any launch for null pointers, empty extents, N % T != 0,
+ * (N/T - 1) * s + 1 > R, or off + 2C > ld; none allocates or synchronises. ws: t2v_cbn_ws_floats floats. */
+int64_t t2v_cbn_ws_floats(int N, int C, int64_t S);
+int t2v_cbn_train_fwd(const float* x, const float* gamma, const float* beta, const float* tab, float* y, float* stats,
+                      float* running_mean, float* running_var, float* ws, int N, int C, int H, int W, int ld, int off, int s, int T,
+                      int R, float momentum, float eps, int relu, int64_t* num_batches_tracked, void* stream);
+/* y is [N,C,2H,2W] */
+int t2v_cbn_train_fwd_up(const float* x, const float* gamma, const float* beta, const float* tab, float* y, float* stats,
+                         float* running_mean, float* running_var, float* ws, int N, int C, int H, int W, int ld, int off, int s,
+                         int T, int R, float momentum, float eps, int relu, int64_t* num_batches_tracked, void* stream);
+int t2v_cbn_train_bwd(const float* gy, const float* x, const float* y, const float* stats, const float* gamma, const float* tab,
+                      float* gx, float* ggamma, float* gbeta, float* gtab, float* ws, int N, int C, int H, int W, int ld, int off,
+                      int s, int T, int R, int relu, void* stream);
+/* gy / y are [N,C,2H,2W] */
+int t2v_cbn_train_bwd_up(const float* gy, const float* x, const float* y, const float* stats, const float* gamma, const float* tab,
+                         float* gx, float* ggamma, float* gbeta, float* gtab, float* ws, int N, int C, int H, int W, int ld, int off,
+                         int s, int T, int R, int relu, void* stream);
+/* either adjoint (`up` = 0 / 1) with gx = the site's input gradient + gx_add (may be NULL), as t2v_bn_train_bwd_add */
+int t2v_cbn_train_bwd_add(const float* gy, const float* x, const float* y, const float* stats, const float* gamma, const float* tab,
+                          const float* gx_add, float* gx, float* ggamma, float* gbeta, float* gtab, float* ws, int N, int C, int H,
+                          int W, int ld, int off, int s, int T, int R, int up, int relu, void* stream);
+int t2v_cbn_eval(const float* x, const float* rm, const float* rv, const float* gamma, const float* beta, const float* tab,
+                 float* y, int N, int C, int H, int W, int ld, int off, int s, int T, int R, float eps, int relu, void* stream);
+
 /* ConvLSTM gate math (conv_lstm.py:32-38, peepholes are constant zeros):
  * pre[B,4,C,S] (order i,f,c,o: the NCHW output of one convolution over the 4 side-by-side packed gate
  * weights) ; c_prev[B,C,S] -> h, c_new; act saved [B,4,C,S] (i,f,g,o after the non-linearities) for the

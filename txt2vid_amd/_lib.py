@@ -177,6 +177,13 @@ SIGNATURES = {
     't2v_bn_train_bwd_up': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     't2v_bn_train_bwd_add': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     't2v_bn_eval': [_P, _P, _P, _P, _P, _P, _I, _I, _L, _F, _I, _P],
+    't2v_cbn_ws_floats': [_I, _I, _L],
+    't2v_cbn_train_fwd': [_P] * 9 + [_I] * 9 + [_F, _F, _I, _P, _P],
+    't2v_cbn_train_fwd_up': [_P] * 9 + [_I] * 9 + [_F, _F, _I, _P, _P],
+    't2v_cbn_train_bwd': [_P] * 11 + [_I] * 9 + [_I, _P],
+    't2v_cbn_train_bwd_up': [_P] * 11 + [_I] * 9 + [_I, _P],
+    't2v_cbn_train_bwd_add': [_P] * 12 + [_I] * 9 + [_I, _I, _P],
+    't2v_cbn_eval': [_P] * 7 + [_I] * 9 + [_F, _I, _P],
     't2v_lstm_gates': [_P, _P, _P, _P, _P, _I, _L, _P],
     't2v_lstm_gates_bwd': [_P, _P, _P, _P, _P, _P, _P, _I, _L, _P],
     't2v_skinny_gemm_splits': [_I, _I, _I],
@@ -264,7 +271,7 @@ SIGNATURES = {
     't2v_version': [],
 }
 _RESTYPE = {'t2v_multi_ws_floats': C.c_int64, 't2v_sn_ws_floats': C.c_int64, 't2v_pool_conv_fwd_ws_floats': C.c_int64, 't2v_pool_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_grouped_bias_slab_floats': C.c_int64, 't2v_conv_fwd_grouped_ws_floats': C.c_int64,
-            't2v_conv_wgrad_grouped_slab_floats': C.c_int64, 't2v_conv_fwd_ws_floats': C.c_int64, 't2v_channel_sum_ws_floats': C.c_int64, 't2v_channel_sum_grouped_ws_floats': C.c_int64, 't2v_bn_ws_floats': C.c_int64, 't2v_version': C.c_char_p}
+            't2v_conv_wgrad_grouped_slab_floats': C.c_int64, 't2v_conv_fwd_ws_floats': C.c_int64, 't2v_channel_sum_ws_floats': C.c_int64, 't2v_channel_sum_grouped_ws_floats': C.c_int64, 't2v_bn_ws_floats': C.c_int64, 't2v_cbn_ws_floats': C.c_int64, 't2v_version': C.c_char_p}
 
 _lib = None
 

@@ -646,6 +646,257 @@ extern "C" int t2v_bn_eval(const float* x, const float* rm, const float* rv, con
     return launch_status();
 }
 
+// ---------------------------------------------------------------- conditional BatchNorm2d (generator, opt-in)
+// One definition (include/t2v_hip.h has the same text): x is [N,C,H,W] with frames merged into the batch, row n belongs to
+// level sample j = n / T and reads base row j * s of the modulation table `tab` [R, ld]; the site owns columns
+// off .. off + 2C laid out [dgamma (C) | dbeta (C)]:
+//     xhat = (x - mean_c) * istd_c                       (batch statistics over all rows: bn_stats_part_k + the Chan merge)
+//     y    = xhat * (gamma_c + tab[j*s, off + c]) + (beta_c + tab[j*s, off + C + c])   -> [ReLU] -> [x2 up-sampling]
+// The statistics never see the affine, so (mean, 1/std), the running statistics and the step counter are those of the
+// plain site, bit for bit: the same statistics kernel and the same serial merge produce them.
+// Backward, two launches like the plain site: (1) cbn_bwd_rows_k leaves sb[n,c] = sum_hw g', sg[n,c] = sum_hw g' * xhat per
+// ROW in the workspace (the plain site leaves them per slice); (2) every workgroup of channel c sums them over n in a fixed
+// order into dbeta, dgamma, A = sum_n Gamma[n,c] sb, B = sum_n Gamma[n,c] sg and writes
+//     dx = istd * (Gamma * g' - A / M - xhat * B / M) [+ the fork's second gradient],
+// its y == 0 workgroup also publishing dgamma, dbeta and the site's columns of dL/dtab for EVERY table row: the sums over
+// a sample's T rows where the level holds base row r (r % s == 0, r / s < N / T), exact zeros elsewhere.
+__device__ __forceinline__ const float* cbn_row(const float* tab, long n, int T, int s, int ld, int off, int c) {
+    return tab + (size_t)(n / T) * s * ld + off + c;
+}
+template <bool UP>
+__global__ __launch_bounds__(256) void cbn_apply_merge_k(const float* x, const float* part, int split, const float* gamma,
+                                                         const float* beta, const float* tab, int ld, int off, int s, int T,
+                                                         float* y, float* stats, float* rmean, float* rvar, int N, int C, long S,
+                                                         float momentum, float eps, int relu, long long* batches_tracked, int W) {
+    const int c = blockIdx.x;
+    if (batches_tracked && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) *batches_tracked += 1;
+    float n = 0.f, mean = 0.f, m2 = 0.f;                 // (the merge of bn_apply_merge_k, statement for statement)
+    for (int k = 0; k < split; ++k) {
+        const float* p = part + ((size_t)c * split + k) * 3;
+        const float nb = p[0];
+        if (nb <= 0.f) continue;
+        const float delta = p[1] - mean, nt = n + nb;
+        mean += delta * (nb / nt);
+        m2 += p[2] + delta * delta * (n * nb / nt);
+        n = nt;
+    }
+    const float var = m2 / n;
+    const float istd = 1.f / sqrtf(var + eps);
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        stats[c] = mean;
+        stats[C + c] = istd;
+        if (rmean) {
+            const float unb = n > 1.f ? m2 / (n - 1.f) : var;
+            rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
+            rvar[c] = (1.f - momentum) * rvar[c] + momentum * unb;
+        }
+    }
+    const float g0 = gamma[c], b0 = beta[c];
+    const long total = (long)N * S;
+    const long per = (total + gridDim.y - 1) / gridDim.y;
+    const long e0 = (long)blockIdx.y * per;
+    long e1 = e0 + per;
+    if (e1 > total) e1 = total;
+    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
+        const long nn = e / S, sp = e - nn * S;
+        const size_t idx = ((size_t)nn * C + c) * S + sp;
+        const float* t = cbn_row(tab, nn, T, s, ld, off, c);
+        float v = (x[idx] - mean) * istd * (g0 + t[0]) + (b0 + t[C]);
+        v = relu ? fmaxf(v, 0.f) : v;
+        if (UP) {
+            const long h = sp / W, w = sp - h * W;
+            float* q = y + (idx - sp) * 4 + (size_t)(2 * h) * (2 * W) + 2 * w;
+            q[0] = v; q[1] = v; q[2 * W] = v; q[2 * W + 1] = v;
+        } else y[idx] = v;
+    }
+}
+// lanes that share one row of the per-row sums: a power of two within a wave (shuffles only), or the whole workgroup
+static int cbn_row_lanes(long S) {
+    if (S > 128) return 256;
+    int g = 1;
+    while (g < S && g < 64) g <<= 1;
+    return g;
+}
+template <bool UP>
+__global__ __launch_bounds__(256) void cbn_bwd_rows_k(const float* gy, const float* x, const float* y, const float* stats,
+                                                      float* rows, int N, int C, long S, int relu, int W, int G) {
+    __shared__ float red[4];
+    const int c = blockIdx.x;
+    const float mean = stats[c], istd = stats[C + c];
+    const long n = (long)blockIdx.y * (256 / G) + threadIdx.x / G;
+    const int lane = threadIdx.x & (G - 1);
+    float s1 = 0.f, s2 = 0.f;
+    if (n < N) {
+        for (long sp = lane; sp < S; sp += G) {
+            const size_t idx = ((size_t)n * C + c) * S + sp;
+            const float g = bn_gy<UP>(gy, y, idx, sp, W, relu);
+            s1 += g;
+            s2 += g * (x[idx] - mean) * istd;
+        }
+    }
+    if (G == 256) {                                      // (uniform over the workgroup)
+        s1 = block_sum(s1, red);
+        s2 = block_sum(s2, red);
+    } else {
+        for (int o = G >> 1; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+    }
+    if (lane == 0 && n < N) {
+        float* p = rows + ((size_t)c * N + n) * 2;
+        p[0] = s1; p[1] = s2;
+    }
+}
+template <bool UP>
+__global__ __launch_bounds__(256) void cbn_bwd_apply_merge_k(const float* gy, const float* x, const float* y, const float* stats,
+                                                             const float* gamma, const float* tab, int ld, int off, int s, int T,
+                                                             int R, const float* rows, float* gx, float* ggamma, float* gbeta,
+                                                             float* gtab, int N, int C, long S, int relu, int W,
+                                                             const float* __restrict__ add) {
+    __shared__ float red[16];
+    const int c = blockIdx.x;
+    const float* r = rows + (size_t)c * N * 2;
+    const float g0 = gamma[c];
+    float sb = 0.f, sg = 0.f, A = 0.f, B = 0.f;
+    for (int n = threadIdx.x; n < N; n += 256) {
+        const float vb = r[2 * n], vg = r[2 * n + 1];
+        const float G = g0 + cbn_row(tab, n, T, s, ld, off, c)[0];
+        sb += vb; sg += vg; A += G * vb; B += G * vg;
+    }
+    sb = wave_sum(sb); sg = wave_sum(sg); A = wave_sum(A); B = wave_sum(B);
+    if ((threadIdx.x & 63) == 0) {
+        float* q = red + (threadIdx.x >> 6) * 4;
+        q[0] = sb; q[1] = sg; q[2] = A; q[3] = B;
+    }
+    __syncthreads();
+    sb = (red[0] + red[4]) + (red[8] + red[12]);
+    sg = (red[1] + red[5]) + (red[9] + red[13]);
+    A = (red[2] + red[6]) + (red[10] + red[14]);
+    B = (red[3] + red[7]) + (red[11] + red[15]);
+    if (blockIdx.y == 0) {
+        if (threadIdx.x == 0) { gbeta[c] = sb; ggamma[c] = sg; }
+        const int held = N / T;                          // samples this level holds
+        for (int row = threadIdx.x; row < R; row += 256) {
+            float db = 0.f, dg = 0.f;
+            if (row % s == 0 && row / s < held) {
+                const float* p = r + (size_t)(row / s) * T * 2;
+                for (int t = 0; t < T; ++t) { db += p[2 * t]; dg += p[2 * t + 1]; }
+            }
+            float* q = gtab + (size_t)row * ld + off + c;
+            q[0] = dg; q[C] = db;
+        }
+    }
+    const float mean = stats[c], istd = stats[C + c];
+    const float invcnt = 1.f / (float)((long)N * S);
+    const float a1 = A * invcnt, a2 = B * invcnt;
+    const long total = (long)N * S;
+    const long per = (total + gridDim.y - 1) / gridDim.y;
+    const long e0 = (long)blockIdx.y * per;
+    long e1 = e0 + per;
+    if (e1 > total) e1 = total;
+    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
+        const long nn = e / S, sp = e - nn * S;
+        const size_t idx = ((size_t)nn * C + c) * S + sp;
+        const float g = bn_gy<UP>(gy, y, idx, sp, W, relu);
+        const float xh = (x[idx] - mean) * istd;
+        const float G = g0 + cbn_row(tab, nn, T, s, ld, off, c)[0];
+        const float v = istd * (G * g - a1 - xh * a2);
+        gx[idx] = add ? v + add[idx] : v;
+    }
+}
+__global__ void cbn_eval_k(const float* x, const float* rm, const float* rv, const float* gamma, const float* beta,
+                           const float* tab, int ld, int off, int s, int T, float* y, int N, int C, long S, float eps, int relu) {
+    const long n = (long)N * C * S;
+    GRID_STRIDE(i, n) {
+        const long pl = i / S;
+        const int c = pl % C;
+        const float* t = cbn_row(tab, pl / C, T, s, ld, off, c);
+        float v = (x[i] - rm[c]) * (1.f / sqrtf(rv[c] + eps)) * (gamma[c] + t[0]) + (beta[c] + t[C]);
+        y[i] = relu ? fmaxf(v, 0.f) : v;
+    }
+}
+// what every entry point checks of the modulation before it launches: rows of T frames, the last base row inside the table,
+// the site's 2C columns inside the leading dimension
+static bool cbn_tab_ok(const float* tab, int ld, int off, int s, int T, int R, int N, int C) {
+    if (!tab || ld < 1 || off < 0 || s < 1 || T < 1 || R < 1 || N < 1 || C < 1) return false;
+    if (N % T != 0) return false;
+    if ((long)(N / T - 1) * s + 1 > (long)R) return false;
+    return (long)off + 2L * C <= (long)ld;
+}
+extern "C" int64_t t2v_cbn_ws_floats(int N, int C, int64_t S) {
+    if (N < 1 || C < 1 || S < 1) return T2V_EINVAL;
+    const int64_t st = (int64_t)C * bn_split(N, C, (long)S) * 3, rw = (int64_t)2 * N * C;
+    return st > rw ? st : rw;
+}
+static int cbn_fwd(bool up, const float* x, const float* gamma, const float* beta, const float* tab, float* y, float* stats, float* rm,
+                   float* rv, float* ws, int N, int C, int H, int W, int ld, int off, int s, int T, int R, float momentum, float eps,
+                   int relu, int64_t* batches_tracked, void* st) {
+    if (!x || !gamma || !beta || !y || !stats || !ws || H < 1 || W < 1 || !cbn_tab_ok(tab, ld, off, s, T, R, N, C)) return T2V_EINVAL;
+    const long S = (long)H * W;
+    const int sp = bn_split(N, C, S);
+    T2V_LAUNCH(bn_stats_part_k, dim3(C, sp), dim3(256), 0, S_(st), x, ws, N, C, S, sp);
+    if (up)
+        T2V_LAUNCH(cbn_apply_merge_k<true>, dim3(C, bn_slices(N, C, S)), dim3(256), 0, S_(st), x, ws, sp, gamma, beta, tab, ld, off, s, T,
+                   y, stats, rm, rv, N, C, S, momentum, eps, relu, (long long*)batches_tracked, W);
+    else
+        T2V_LAUNCH(cbn_apply_merge_k<false>, dim3(C, bn_slices(N, C, S)), dim3(256), 0, S_(st), x, ws, sp, gamma, beta, tab, ld, off, s, T,
+                   y, stats, rm, rv, N, C, S, momentum, eps, relu, (long long*)batches_tracked, 1);
+    return launch_status();
+}
+static int cbn_bwd(bool up, const float* gy, const float* x, const float* y, const float* stats, const float* gamma, const float* tab,
+                   const float* gx_add, float* gx, float* ggamma, float* gbeta, float* gtab, float* ws, int N, int C, int H, int W,
+                   int ld, int off, int s, int T, int R, int relu, void* st) {
+    if (!gy || !x || !stats || !gamma || !gx || !ggamma || !gbeta || !gtab || !ws || H < 1 || W < 1 ||
+        !cbn_tab_ok(tab, ld, off, s, T, R, N, C))
+        return T2V_EINVAL;
+    if (relu && !y) return T2V_EINVAL;
+    const long S = (long)H * W;
+    const int G = cbn_row_lanes(S);
+    const dim3 rgrid(C, (N + 256 / G - 1) / (256 / G)), agrid(C, bn_slices(N, C, S));
+    if (up) {
+        T2V_LAUNCH(cbn_bwd_rows_k<true>, rgrid, dim3(256), 0, S_(st), gy, x, y, stats, ws, N, C, S, relu, W, G);
+        T2V_LAUNCH(cbn_bwd_apply_merge_k<true>, agrid, dim3(256), 0, S_(st), gy, x, y, stats, gamma, tab, ld, off, s, T, R,
+                   (const float*)ws, gx, ggamma, gbeta, gtab, N, C, S, relu, W, gx_add);
+    } else {
+        T2V_LAUNCH(cbn_bwd_rows_k<false>, rgrid, dim3(256), 0, S_(st), gy, x, y, stats, ws, N, C, S, relu, 1, G);
+        T2V_LAUNCH(cbn_bwd_apply_merge_k<false>, agrid, dim3(256), 0, S_(st), gy, x, y, stats, gamma, tab, ld, off, s, T, R,
+                   (const float*)ws, gx, ggamma, gbeta, gtab, N, C, S, relu, 1, gx_add);
+    }
+    return launch_status();
+}
+extern "C" int t2v_cbn_train_fwd(const float* x, const float* gamma, const float* beta, const float* tab, float* y, float* stats,
+                                 float* rm, float* rv, float* ws, int N, int C, int H, int W, int ld, int off, int s, int T, int R,
+                                 float momentum, float eps, int relu, int64_t* batches_tracked, void* st) {
+    return cbn_fwd(false, x, gamma, beta, tab, y, stats, rm, rv, ws, N, C, H, W, ld, off, s, T, R, momentum, eps, relu, batches_tracked, st);
+}
+extern "C" int t2v_cbn_train_fwd_up(const float* x, const float* gamma, const float* beta, const float* tab, float* y, float* stats,
+                                    float* rm, float* rv, float* ws, int N, int C, int H, int W, int ld, int off, int s, int T, int R,
+                                    float momentum, float eps, int relu, int64_t* batches_tracked, void* st) {
+    return cbn_fwd(true, x, gamma, beta, tab, y, stats, rm, rv, ws, N, C, H, W, ld, off, s, T, R, momentum, eps, relu, batches_tracked, st);
+}
+extern "C" int t2v_cbn_train_bwd(const float* gy, const float* x, const float* y, const float* stats, const float* gamma,
+                                 const float* tab, float* gx, float* ggamma, float* gbeta, float* gtab, float* ws, int N, int C, int H,
+                                 int W, int ld, int off, int s, int T, int R, int relu, void* st) {
+    return cbn_bwd(false, gy, x, y, stats, gamma, tab, nullptr, gx, ggamma, gbeta, gtab, ws, N, C, H, W, ld, off, s, T, R, relu, st);
+}
+extern "C" int t2v_cbn_train_bwd_up(const float* gy, const float* x, const float* y, const float* stats, const float* gamma,
+                                    const float* tab, float* gx, float* ggamma, float* gbeta, float* gtab, float* ws, int N, int C,
+                                    int H, int W, int ld, int off, int s, int T, int R, int relu, void* st) {
+    return cbn_bwd(true, gy, x, y, stats, gamma, tab, nullptr, gx, ggamma, gbeta, gtab, ws, N, C, H, W, ld, off, s, T, R, relu, st);
+}
+extern "C" int t2v_cbn_train_bwd_add(const float* gy, const float* x, const float* y, const float* stats, const float* gamma,
+                                     const float* tab, const float* gx_add, float* gx, float* ggamma, float* gbeta, float* gtab,
+                                     float* ws, int N, int C, int H, int W, int ld, int off, int s, int T, int R, int up, int relu,
+                                     void* st) {
+    return cbn_bwd(up != 0, gy, x, y, stats, gamma, tab, gx_add, gx, ggamma, gbeta, gtab, ws, N, C, H, W, ld, off, s, T, R, relu, st);
+}
+extern "C" int t2v_cbn_eval(const float* x, const float* rm, const float* rv, const float* gamma, const float* beta, const float* tab,
+                            float* y, int N, int C, int H, int W, int ld, int off, int s, int T, int R, float eps, int relu, void* st) {
+    if (!x || !rm || !rv || !gamma || !beta || !y || H < 1 || W < 1 || !cbn_tab_ok(tab, ld, off, s, T, R, N, C)) return T2V_EINVAL;
+    const long S = (long)H * W;
+    T2V_LAUNCH(cbn_eval_k, dim3(nblocks((long)N * C * S)), dim3(256), 0, S_(st), x, rm, rv, gamma, beta, tab, ld, off, s, T, y, N, C, S,
+               eps, relu);
+    return launch_status();
+}
+
 // ---------------------------------------------------------------- ConvLSTM gates
 __device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + expf(-v)); }
 

@@ -46,10 +46,16 @@ class Linear(nn.Linear):
 class BatchNorm2d(nn.BatchNorm2d):
     """Training-mode batch statistics / eval-mode running statistics, optional fused ReLU."""
 
-    def forward(self, x, relu=False, up=False, fork=False):
-        """`fork`: returns (y, x') — x' is x for its second consumer (functional.BatchNormActFork)."""
+    def forward(self, x, relu=False, up=False, fork=False, mod=None):
+        """`fork`: returns (y, x') — x' is x for its second consumer (functional.BatchNormActFork).
+        `mod`: this forward's conditional modulation of the site (functional_cbn.Modulation.site; None: the plain BatchNorm)."""
         if self.momentum is None or not self.affine or not self.track_running_stats:
             raise NotImplementedError('only the default BatchNorm2d configuration is on the hot path')
+        if mod is not None:
+            from ..functional_cbn import cond_batch_norm_act
+            return cond_batch_norm_act(x, self.weight, self.bias, self.running_mean, self.running_var, self.training, mod,
+                                       self.momentum, self.eps, relu, counter=self.num_batches_tracked if self.training else None,
+                                       up=up, fork=fork)
         return TF.batch_norm_act(x, self.weight, self.bias, self.running_mean, self.running_var, self.training,
                                  self.momentum, self.eps, relu, counter=self.num_batches_tracked if self.training else None, up=up,
                                  fork=fork)
@@ -217,21 +223,25 @@ class UpBlock(nn.Module):
         if with_non_local:
             self.attn = Attention(out_channels)
 
-    def forward(self, x):
+    def forward(self, x, mod=None):
+        """`mod`: the conditional modulation of the block's two BatchNorm sites for this forward, (first, second), or None."""
         m = self.main.inner_module
+        if mod is not None and not (isinstance(m[0], BatchNorm2d) and isinstance(m[4], BatchNorm2d)):
+            raise NotImplementedError('conditional BatchNorm needs the HIP BatchNorm2d sites')
+        mod0, mod1 = mod if mod is not None else (None, None)
         # (the block input feeds the BatchNorm and the skip path: the BatchNorm adjoint sums the skip path's gradient in its own pass)
         if isinstance(m[0], BatchNorm2d) and isinstance(m[2], Upsample) and isinstance(m[3], Conv2d) and TF.up_conv_ok(x, m[3].weight):
             # Up -> conv3x3 without the up-sampled tensor: 9 taps per INPUT pixel (a quarter of the MACs), functional_pool.py
             _check_same_conv(m[3])
-            h, x = m[0](x, relu=True, fork=True)
+            h, x = m[0](x, relu=True, fork=True, mod=mod0)
             h = TF.up_conv(h, m[3].weight, m[3].bias)
         elif isinstance(m[0], BatchNorm2d) and isinstance(m[2], Upsample):
-            h, x = m[0](x, relu=True, up=True, fork=True)                              # BN+ReLU+Up fused
+            h, x = m[0](x, relu=True, up=True, fork=True, mod=mod0)                              # BN+ReLU+Up fused
             h = m[3](h)
         else:
-            h = m[0](x, relu=True) if isinstance(m[0], BatchNorm2d) else m[1](m[0](x))
+            h = m[0](x, relu=True, mod=mod0) if isinstance(m[0], BatchNorm2d) else m[1](m[0](x))
             h = m[3](m[2](h))
-        h = m[4](h, relu=True) if isinstance(m[4], BatchNorm2d) else m[5](m[4](h))
+        h = m[4](h, relu=True, mod=mod1) if isinstance(m[4], BatchNorm2d) else m[5](m[4](h))
         h = m[6](h)
         idm = self.main.identity_map
         if isinstance(idm, Upsample):
@@ -338,11 +348,14 @@ class RenderBlock(nn.Module):
         self.conv = which_conv(in_channels, out_channels, kernel_size=3, padding=1)
         self.final = Tanh()
 
-    def forward(self, x, fork=False):
-        """`fork`: returns (image, x') — x' is the map for the next level (its gradient joins the BatchNorm adjoint's pass)."""
+    def forward(self, x, fork=False, mod=None):
+        """`fork`: returns (image, x') — x' is the map for the next level (its gradient joins the BatchNorm adjoint's pass).
+        `mod`: the conditional modulation of the block's BatchNorm site for this forward, or None."""
+        if mod is not None and not isinstance(self.bn, BatchNorm2d):
+            raise NotImplementedError('conditional BatchNorm needs the HIP BatchNorm2d site')
         if fork and isinstance(self.bn, BatchNorm2d):
-            h, x = self.bn(x, relu=True, fork=True)
+            h, x = self.bn(x, relu=True, fork=True, mod=mod)
             return self.final(self.conv(h)), x
-        h = self.bn(x, relu=True) if isinstance(self.bn, BatchNorm2d) else self.activation(self.bn(x))
+        h = self.bn(x, relu=True, mod=mod) if isinstance(self.bn, BatchNorm2d) else self.activation(self.bn(x))
         r = self.final(self.conv(h))
         return (r, x) if fork else r
