@@ -786,6 +786,36 @@ typedef struct t2v_lecam_grad {
 int t2v_lecam_fwd(float* lecam, const t2v_ada_level* levels, int n, float decay, int start, float* saved, float* out, void* stream);
 int t2v_lecam_bwd(const t2v_lecam_grad* levels, int n, const float* saved, const float* g, void* stream);
 
+/* ---- projection head of the text-conditioned discriminator (Miyato & Koyama 2018; opt-in, Resnet3D(proj=True)) ------
+ * One definition. V [K, J] row-major = `proj.weight` (K = trunk features, J = cond_dim). The conditional logit of row b gains
+ *   sum_k sum_j f[b,k] V[k,j] s[b,j]            (f the trunk's spatially summed features, s the sentence code)
+ * on top of the existing head fc(cat(f, s)). The term is the trilinear form T(g, f, s; V) = sum_b g[b] sum_kj f[b,k] V[k,j] s[b,j];
+ * each derivative of T is T with one index left free, so four roles close the family under differentiation to any order:
+ *   t2v_proj_rows    out y [b]    = (base ? base[b] : 0) + sum_kj f[b,k] V[k,j] s[b,j]          reads f, s, base (may be NULL)
+ *   t2v_proj_feat    out F [b, K] = g[b] * sum_j V[k,j] s[b,j]                                    reads g, s
+ *   t2v_proj_cond    out C [b, J] = g[b] * sum_k f[b,k] V[k,j]                                    reads g, f
+ *   t2v_proj_weight  W [K, J] (+= if accum) sum over members, then rows, of g[b] f[b,k] s[b,j]    reads g, f, s
+ * One launch serves up to T2V_MAX_GROUPS members (pyramid levels, batch halves) that share V / W, each with its own row count
+ * b >= 1; `members` is a HOST array whose descriptors travel by value in the kernel arguments. A role ignores the member
+ * pointers it does not read. g, base and y are dense [b] (the [b, 1] logits), f [b, K], s [b, J]; out must not alias an input.
+ * fp32. Every sum runs in a fixed order (per-lane partials, wave reduction, sixteen waves through LDS; the weight role
+ * walks members and rows in order in one thread per element): plain vector stores, no atomics, no workspace, the same bits run
+ * to run. Any K >= 1 and J >= 1. None allocates or synchronises; all can be captured.
+ * T2V_EINVAL, before any launch, on members == NULL, V / W == NULL, n outside 1..T2V_MAX_GROUPS, K < 1, J < 1, a member with
+ * b < 1, or a NULL pointer among those the role reads or writes (base excepted). */
+typedef struct t2v_proj_member {
+    const float* g;      /* [b]: dL/dy, or whatever stands in its place in a higher derivative */
+    const float* f;      /* [b, K] */
+    const float* s;      /* [b, J] */
+    const float* base;   /* rows only: [b] added to the term, or NULL */
+    float* out;          /* rows: y [b]; feat: F [b, K]; cond: C [b, J]; weight: unused */
+    int32_t b, reserved;
+} t2v_proj_member;
+int t2v_proj_rows(const t2v_proj_member* members, int n, const float* V, int K, int J, void* stream);
+int t2v_proj_feat(const t2v_proj_member* members, int n, const float* V, int K, int J, void* stream);
+int t2v_proj_cond(const t2v_proj_member* members, int n, const float* V, int K, int J, void* stream);
+int t2v_proj_weight(const t2v_proj_member* members, int n, float* W, int K, int J, int accum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

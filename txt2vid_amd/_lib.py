@@ -108,6 +108,12 @@ class LecamGrad(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class ProjMember(C.Structure):
+    """t2v_proj_member (include/t2v_hip.h)."""
+    _fields_ = [('g', C.c_void_p), ('f', C.c_void_p), ('s', C.c_void_p), ('base', C.c_void_p), ('out', C.c_void_p), ('b', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 MAX_GROUPS = 8
 _P = C.c_void_p
 _I = C.c_int
@@ -266,6 +272,10 @@ SIGNATURES = {
     't2v_ada_update': [_P, _P, _I, _F, _F, _I, _P],
     't2v_lecam_fwd': [_P, _P, _I, _F, _I, _P, _P, _P],
     't2v_lecam_bwd': [_P, _I, _P, _P, _P],
+    't2v_proj_rows': [_P, _I, _P, _I, _I, _P],
+    't2v_proj_feat': [_P, _I, _P, _I, _I, _P],
+    't2v_proj_cond': [_P, _I, _P, _I, _I, _P],
+    't2v_proj_weight': [_P, _I, _P, _I, _I, _I, _P],
     't2v_prof_begin': [_I],
     't2v_prof_end': [C.POINTER(C.c_double), _I],
     't2v_version': [],

@@ -2829,6 +2829,9 @@ def _pass_none_through(cls):
 # the pooled second convolution of the discriminator blocks (box-sum + stride-2 GEMMs): functional_pool.py
 from .functional_pool import (pool_conv_ok, pool_conv_group, pool_tmode, PoolConvG, PoolConvDgradG, PoolConvWgradG, boxsum_raw, unbox_raw,     # noqa: E402,F401
                               pool_fwd_raw, pool_dgrad_raw, pool_wgrad_raw, up_conv, up_conv_ok, UpConvFn)
+# the projection head of the text-conditioned discriminator (opt-in): functional_proj.py
+from .functional_proj import (proj_rows_group, proj_rows_raw, proj_feat_raw, proj_cond_raw, proj_weight_raw, ProjRowsG, ProjFeatG,     # noqa: E402,F401
+                              ProjCondG, ProjWeightG)
 
 
 def add_group(as_, bs):

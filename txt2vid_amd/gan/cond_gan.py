@@ -318,6 +318,8 @@ class CondGan(object):
             self.cond_encoder.load_state_dict(to_load['cond'])
         for name, d in zip(self.discrim_names, self.discrims):
             if name in to_load:
+                if hasattr(d, 'refuse_proj_mismatch'):
+                    d.refuse_proj_mismatch(to_load[name])          # (before the key matching, which keeps the wanted keys only)
                 d.load_state_dict(_match_keys(to_load[name], d.state_dict().keys()))
         if self.gen_ema is not None:
             # a file without the key (written without --G_ema, or by the reference) leaves the average a copy of the loaded `gen`;

@@ -7,11 +7,34 @@ from .. import functional as TF
 from .layers import ResidualBlock, DownBlock, Attention3d, Conv3d, AvgPool3d, ReLU, Linear, down_block_levels, nonlocal_levels
 
 
+_PROJ_MISMATCH = ('discriminator checkpoint %s projection head (proj.weight key) but this discriminator was built with proj=%s: '
+                  'pass the same proj in the --D spec')
+
+
+class CondProjection(nn.Module):
+    """The weight of the projection head (`Resnet3D(proj=True)`, Miyato & Koyama 2018; not in the reference): `weight` = V
+    [in_ch, cond_dim] adds featᵀ V s to the conditional logit (functional_proj.py). V starts as zeros and `init()` walks past
+    this class without drawing, so a fresh proj discriminator computes what the plain one computes and every other layer's host
+    draws are unchanged; dL/dV is not zero there, so training moves it. Not an nn.Linear: `--D_sn` leaves V alone."""
+
+    def __init__(self, in_features, cond_dim):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(int(in_features), int(cond_dim)))
+
+    def forward(self, feats, conds, bases):
+        """bases[i] + ((feats[i] @ V) * conds[i]).sum(1, keepdim=True) for every member, one launch."""
+        return TF.proj_rows_group(self.weight, feats, conds, bases)
+
+
 class Resnet3D(nn.Module):
 
     def __init__(self, num_channels=1, mid_ch=64, which_conv=None, which_pool=None, cond_dim=0, num_down_blocks=4,
-                 wide=False, with_attn=True):
+                 wide=False, with_attn=True, proj=False):
         super().__init__()
+        # proj: the conditional logit gains the bilinear term featᵀ V s of a projection discriminator (functional_proj.py; not in
+        # the reference, off by default). proj = False builds exactly the reference's module.
+        if proj and cond_dim < 1:
+            raise ValueError('proj (projection head) needs a sentence code (cond_dim > 0): it cannot run with --dont_use_sent')
         which_conv = which_conv or Conv3d
         which_pool = which_pool or AvgPool3d
         self.activation = ReLU()
@@ -29,6 +52,8 @@ class Resnet3D(nn.Module):
         self.fc_uncond = Linear(in_ch, 1)
         if cond_dim > 0:
             self.fc = Linear(in_ch + cond_dim, 1)
+        if proj:
+            self.proj = CondProjection(in_ch, cond_dim)           # registered after fc: one trailing state-dict key
 
     def groupable(self):
         m = self.res_block.inner_module
@@ -96,12 +121,36 @@ class Resnet3D(nn.Module):
         """`self.fc(torch.cat((features, cond), 1))` (resnet3d.py:53-55) for several levels / members at once: one launch for
         all concatenations, one for all heads (instead of two copies + one linear per member)."""
         feats, conds = list(feats), list(conds)
+        proj = getattr(self, 'proj', None)
         if not (1 <= len(feats) <= TF.MAX_GROUPS) or not feats[0].is_cuda:
-            return [self.fc(TF.cat_features(f, c)) for f, c in zip(feats, conds)]
+            return [self._cond_head(f, c) for f, c in zip(feats, conds)]
+        feats_p, conds_p = feats, conds
+        if proj is not None:
+            # features and sentence codes feed the existing head AND the projection term: grouped forks sum the two gradients of
+            # all members in one launch each (tensors without a gradient pass through)
+            feats, feats_p = TF.fork_group(feats)
+            conds, conds_p = TF.fork_group(conds)
         cats = TF.cat_features_group(feats, conds)
         w5 = self.fc.weight.view(self.fc.weight.shape + (1, 1, 1))
         cs = TF.conv_group([c.view(c.shape + (1, 1, 1)) for c in cats], w5, self.fc.bias)
-        return [c.view(c.shape[0], c.shape[1]) for c in cs]
+        cs = [c.view(c.shape[0], c.shape[1]) for c in cs]
+        return cs if proj is None else proj(feats_p, conds_p, cs)
+
+    def _cond_head(self, feat, cond):
+        """The conditional head of one member: the same values as `cond_heads` on a list of one."""
+        proj = getattr(self, 'proj', None)
+        if proj is None:
+            return self.fc(TF.cat_features(feat, cond))
+        (f, f_p), (s, s_p) = TF.fork_group([feat]), TF.fork_group([cond])
+        return proj(f_p, s_p, [self.fc(TF.cat_features(f[0], s[0]))])[0]
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """A checkpoint written with the projection head (`proj.weight`) loads only into a trunk built with proj=True, and one
+        without into one without: a clear error instead of a bare missing / unexpected key."""
+        has = 'proj.weight' in state_dict
+        if has != hasattr(self, 'proj'):
+            raise ValueError(_PROJ_MISMATCH % ('has' if has else 'has no', hasattr(self, 'proj')))
+        return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def forward(self, x=None, cond=None, xbar=None, computed_features=None):
         uncond = None
@@ -119,6 +168,6 @@ class Resnet3D(nn.Module):
             computed_features = x
             uncond = self.fc_uncond(x)
         if cond is not None:
-            c = self.fc(TF.cat_features(x, cond))
+            c = self._cond_head(x, cond)
             return uncond, c, computed_features
         return uncond, None, computed_features

@@ -2,26 +2,45 @@
 txt2vid/models/tganv2/discrim.py:7-31 (state_dict keys `single_discrim.*`)."""
 import torch.nn as nn
 
-from ..resnet3d import Resnet3D
+from ..resnet3d import Resnet3D, _PROJ_MISMATCH
 
 
 class MultiScaleDiscrim(nn.Module):
     _wrap = False
 
     def __init__(self, discrim_down_blocks=[4, 4, 4, 4], num_channels=3, cond_dim=0, underlying_discrim=Resnet3D,
-                 single_discrim=True):
+                 single_discrim=True, proj=False):
         super().__init__()
+        # proj: the projection head of every underlying discriminator (models/resnet3d.py; not in the reference, off by default)
+        self.proj_on = bool(proj)
+        if self.proj_on and not self._wrap:
+            raise ValueError('proj (projection head) needs the text-conditioned discriminator '
+                             'txt2vid.models.tganv2_cond.discrim.MultiScaleDiscrim')
+        if self.proj_on and cond_dim < 1:
+            raise ValueError('proj (projection head) needs a sentence code (cond_dim > 0): it cannot run with --dont_use_sent')
+        extra = {'proj': True} if self.proj_on else {}
         if single_discrim:
-            d = underlying_discrim(cond_dim=cond_dim, num_down_blocks=discrim_down_blocks[-1], num_channels=num_channels)
+            d = underlying_discrim(cond_dim=cond_dim, num_down_blocks=discrim_down_blocks[-1], num_channels=num_channels, **extra)
             self.single_discrim = _ModuleWrap(d) if self._wrap else d
             self.sub_discrims = [self.single_discrim for _ in discrim_down_blocks]
         else:
             self.single_discrim = None
             subs = []
             for db in discrim_down_blocks:
-                d = underlying_discrim(cond_dim=cond_dim, num_down_blocks=db, num_channels=num_channels)
+                d = underlying_discrim(cond_dim=cond_dim, num_down_blocks=db, num_channels=num_channels, **extra)
                 subs.append(_ModuleWrap(d) if self._wrap else d)
             self.sub_discrims = nn.ModuleList(subs)
+
+    def refuse_proj_mismatch(self, state_dict):
+        """A checkpoint written with the projection head (`*.proj.weight` keys) loads only into a discriminator built with
+        proj=True, and one without into one without: a clear error instead of a bare missing / unexpected key."""
+        has = any(k.endswith('proj.weight') for k in state_dict)
+        if has != self.proj_on:
+            raise ValueError(_PROJ_MISMATCH % ('has' if has else 'has no', self.proj_on))
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        self.refuse_proj_mismatch(state_dict)
+        return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def forward(self, x=None, cond=None, xbar=None, computed_features=None):
         if self.single_discrim is not None and xbar is None and len(x) > 1 and x[0].is_cuda:
