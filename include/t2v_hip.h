@@ -251,7 +251,10 @@ int t2v_upsample2x_add(const float* x, const float* h, float* y, int64_t planes,
 
 /* BatchNorm2d, training mode (layers.py:171,175,249): per-channel batch statistics over (N,H,W),
  * running stats updated with `momentum` (unbiased variance), y = relu?((x-mean)*invstd*gamma+beta).
- * stats[0:C] = mean, stats[C:2C] = invstd (saved for backward). */
+ * stats[0:C] = mean, stats[C:2C] = invstd (saved for backward).
+ * Every entry point that launches a statistics, adjoint-sum or fused apply pass (all but t2v_bn_apply / t2v_bn_eval, and the
+ * conditional t2v_cbn_train_* below) walks a plane with 32-bit arithmetic: S = H * W above 2^31 - 1 is T2V_EINVAL. The `up`
+ * forms move the two adjacent copies of a row as one 8-byte access at a 4-byte aligned address. */
 int64_t t2v_bn_ws_floats(int N, int C, int64_t S);   /* floats of `ws` for bn_stats / bn_bwd */
 /* Launch plan of every entry point below (host arithmetic, no launch): out[0] = slices per channel of the statistics
  * passes (1..64), out[1] = workgroups per channel of the fused merge + apply passes. Used by the tests to assert which

@@ -308,27 +308,139 @@ extern "C" int t2v_upsample2x_bwd(const float* gy, float* gx, int64_t planes, in
 
 // ---------------------------------------------------------------- BatchNorm2d (training)
 // Statistics in two deterministic stages: grid (C, SPLIT) workgroups compute (count, mean, M2) of a
-// contiguous slice of their channel (two passes over the slice, which stays in L2), the finalize kernel
-// merges the slices with Chan's parallel-variance formula and updates the running statistics.
+// contiguous slice of their channel (mean first, then M2 about it: from the values a thread kept in registers, or from a
+// second pass over the slice, which stays in L2), the finalize kernel merges the slices with Chan's parallel-variance
+// formula and updates the running statistics.
 #define BN_MAXSPLIT 64
-__device__ __forceinline__ float bn_elem(const float* x, long e, int C, int c, long S) {
-    const long n = e / S, sp = e - n * S;
-    return x[((size_t)n * C + c) * S + sp];
+// The slice walker of the two-launch training passes. A workgroup owns elements [e0, e1) of channel c in (sample, position)
+// order — slice `slice` of `nslices` equal cuts of N * S — and thread t visits e0 + t, e0 + t + 256, ...: one 64-bit division
+// at entry, then 256 / S samples and 256 % S positions further per step, with a carry, in 32 bits (the launchers hold S
+// below 2^31). UP also keeps the column w = sp % W: the top-left copy of the element in the up-sampled map is 4 * idx - 2 * w.
+#ifndef BN_UNROLL
+#define BN_UNROLL 8            // elements of a trip: their loads are issued together, the arithmetic follows in element order
+#endif
+#define BN_MAX_PLANE 0x7fffffffL    // largest H * W the walker's 32-bit plane arithmetic takes (an 8 GiB plane)
+#ifndef BN_REG_CAP
+#define BN_REG_CAP 32          // values of its slice a statistics thread keeps in registers for the second moment
+#endif
+// The per-element arithmetic below spells out which multiply-adds are fused: with several elements of a trip in flight the
+// compiler is free to pair their operations, and what it pairs it no longer contracts, so "whatever -ffp-contract makes of
+// it" would not keep the rounding these passes have always had.
+#define BN_FMA(a, b, c) __builtin_fmaf((a), (b), (c))
+#define BN_NO_CONTRACT _Pragma("clang fp contract(off)")
+static_assert(BN_REG_CAP % BN_UNROLL == 0, "the statistics pass fills its registers in whole trips");
+typedef float bn_f2 __attribute__((ext_vector_type(2)));
+typedef bn_f2 bn_f2u __attribute__((aligned(4)));          // an 8-byte access at a 4-byte aligned address
+template <bool UP>
+struct BnWalk {
+    size_t idx;                // offset of the element in x: (n * C + c) * S + sp
+    long m, cnt;               // elements this thread has in the slice; elements of the whole slice
+    int n;                     // its sample
+    unsigned sp, w;            // position in the plane, column
+    size_t step, wrap;         // (the strides below are the same in every thread)
+    unsigned S, W, dr, dw;
+    int dq;
+    __device__ __forceinline__ BnWalk(int N, int C, long S_, int W_, int c, int nslices, int slice, int t) {
+        const long total = (long)N * S_;
+        const long per = (total + nslices - 1) / nslices;
+        const long e0 = (long)slice * per;
+        long e1 = e0 + per;
+        if (e1 > total) e1 = total;
+        cnt = e1 > e0 ? e1 - e0 : 0;
+        m = cnt > t ? (cnt - t + 255) >> 8 : 0;
+        const long e = e0 + t;
+        const long q = e / S_;
+        n = (int)q;
+        S = (unsigned)S_; W = (unsigned)W_;
+        sp = (unsigned)(e - q * S_);
+        idx = ((size_t)q * C + c) * S + sp;
+        dq = (int)(256u / S); dr = 256u % S;
+        step = (size_t)dq * C * S + dr;
+        wrap = (size_t)(C - 1) * S;
+        w = UP ? sp % W : 0u; dw = UP ? 256u % W : 0u;
+    }
+    __device__ __forceinline__ void next() {
+        idx += step; n += dq; sp += dr;
+        if (sp >= S) { sp -= S; idx += wrap; n += 1; }
+        if (UP) { w += dw; if (w >= W) w -= W; }
+    }
+    __device__ __forceinline__ size_t up() const { return idx * 4 - 2 * (size_t)w; }
+};
+// one trip: up to BN_UNROLL elements (`left` of them remain) are loaded, the walker moving on, ...
+template <class T, class Wk, class Load>
+__device__ __forceinline__ void bn_trip_load(T* v, Wk& wk, long left, Load load) {
+    if (left >= BN_UNROLL) {
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) { v[k] = load(wk); wk.next(); }
+    } else {                                             // the ragged tail: predicated, no neutral element is added in
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL - 1; ++k)
+            if (k < left) { v[k] = load(wk); wk.next(); }
+    }
+}
+// ... and then consumed in element order
+template <class T, class Use>
+__device__ __forceinline__ void bn_trip_use(const T* v, long left, Use use) {
+    if (left >= BN_UNROLL) {
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL; ++k) use(v[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < BN_UNROLL - 1; ++k)
+            if (k < left) use(v[k]);
+    }
+}
+// a thread's walk over its elements, trip by trip, in two halves: bn_first loads the first trip, bn_rest consumes it and runs
+// the others. A kernel that calls bn_first in front of work that does not depend on the elements (the merge of the channel's
+// partials) has that work cover the loads.
+template <class T, class Wk, class Load>
+__device__ __forceinline__ void bn_first(T* v, Wk& wk, Load load) {
+    if (wk.m > 0) bn_trip_load(v, wk, wk.m, load);
+}
+template <class T, class Wk, class Load, class Use>
+__device__ __forceinline__ void bn_rest(const T* v, Wk& wk, Load load, Use use) {
+    long left = wk.m;
+    if (left > 0) bn_trip_use(v, left, use);
+    for (left -= BN_UNROLL; left > 0; left -= BN_UNROLL) {
+        T u[BN_UNROLL];
+        bn_trip_load(u, wk, left, load);
+        bn_trip_use(u, left, use);
+    }
+}
+template <class T, class Wk, class Load, class Use>
+__device__ __forceinline__ void bn_for_each(Wk wk, Load load, Use use) {
+    T v[BN_UNROLL];
+    bn_first(v, wk, load);
+    bn_rest(v, wk, load, use);
 }
 __global__ __launch_bounds__(256) void bn_stats_part_k(const float* x, float* part, int N, int C, long S, int split) {
     __shared__ float red[4];
     const int c = blockIdx.x;
-    const long total = (long)N * S;
-    const long per = (total + split - 1) / split;
-    const long e0 = (long)blockIdx.y * per;
-    long e1 = e0 + per;
-    if (e1 > total) e1 = total;
-    const long cnt = e1 > e0 ? e1 - e0 : 0;
+    const BnWalk<false> wk(N, C, S, 1, c, split, blockIdx.y, threadIdx.x);
+    const long cnt = wk.cnt;
+    const auto ld = [&](const BnWalk<false>& k) { return x[k.idx]; };
+    // a thread with at most BN_REG_CAP elements keeps them for the second pass; one with more reads its slice (which
+    // stays in L2) again, in the same order
+    const bool keep = wk.m <= BN_REG_CAP;
+    float v[BN_REG_CAP];
     float acc = 0.f;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) acc += bn_elem(x, e, C, c, S);
+    if (keep) {
+        BnWalk<false> k1 = wk;
+#pragma unroll
+        for (int j = 0; j < BN_REG_CAP; j += BN_UNROLL)
+            if (j < wk.m) {
+                bn_trip_load(v + j, k1, wk.m - j, ld);
+                bn_trip_use(v + j, wk.m - j, [&](float xv) { acc += xv; });
+            }
+    } else bn_for_each<float>(wk, ld, [&](float xv) { acc += xv; });
     const float mean = cnt > 0 ? block_sum(acc, red) / (float)cnt : 0.f;
     acc = 0.f;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) { const float d = bn_elem(x, e, C, c, S) - mean; acc += d * d; }
+    const auto sq = [&](float xv) { const float d = xv - mean; acc = BN_FMA(d, d, acc); };       // acc += d * d
+    if (keep) {
+#pragma unroll
+        for (int j = 0; j < BN_REG_CAP; j += BN_UNROLL)
+            if (j < wk.m) bn_trip_use(v + j, wk.m - j, sq);
+    } else bn_for_each<float>(wk, ld, sq);
     const float m2 = block_sum(acc, red);
     if (threadIdx.x == 0) {
         float* p = part + ((size_t)c * split + blockIdx.y) * 3;
@@ -396,25 +508,51 @@ __device__ __forceinline__ float bn_gy(const float* gy, const float* y, size_t i
     if (relu && !(y[o] > 0.f)) g = 0.f;
     return g;
 }
+// the same gradient from a walker, in two halves: what one element loads (the 2x2 copies as two 8-byte reads, the mask
+// value only under ReLU, x, the fork's second gradient if there is one) and the arithmetic on it
+struct BnGrad {
+    float g0, g1, g2, g3;      // !UP: g0 = gy; UP: the upper and the lower pair of copies
+    float yv, xv, add;
+    size_t idx;
+    float tg;                  // (the conditional twin's table entry)
+};
+template <bool UP>
+__device__ __forceinline__ BnGrad bn_grad_load(const float* gy, const float* x, const float* y, const float* add,
+                                               const BnWalk<UP>& k, int relu) {
+    BnGrad e = {};
+    const size_t o = UP ? k.up() : k.idx;
+    if (UP) {
+        const bn_f2 a = *(const bn_f2u*)(gy + o), b = *(const bn_f2u*)(gy + o + 2 * (size_t)k.W);
+        e.g0 = a.x; e.g1 = a.y; e.g2 = b.x; e.g3 = b.y;
+    } else e.g0 = gy[o];
+    e.yv = relu ? y[o] : 1.f;
+    e.xv = x[k.idx];
+    e.add = add ? add[k.idx] : 0.f;
+    e.idx = k.idx;
+    return e;
+}
+template <bool UP>
+__device__ __forceinline__ float bn_grad(const BnGrad& e, int relu) {
+    float g = UP ? (e.g0 + e.g1) + (e.g2 + e.g3) : e.g0;
+    if (relu && !(e.yv > 0.f)) g = 0.f;
+    return g;
+}
 template <bool UP>
 __global__ __launch_bounds__(256) void bn_bwd_part_k(const float* gy, const float* x, const float* y, const float* stats,
                                                      float* part, int N, int C, long S, int relu, int split, int W) {
     __shared__ float red[4];
     const int c = blockIdx.x;
     const float mean = stats[c], istd = stats[C + c];
-    const long total = (long)N * S;
-    const long per = (total + split - 1) / split;
-    const long e0 = (long)blockIdx.y * per;
-    long e1 = e0 + per;
-    if (e1 > total) e1 = total;
     float s1 = 0.f, s2 = 0.f;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
-        const long n = e / S, sp = e - n * S;
-        const size_t idx = ((size_t)n * C + c) * S + sp;
-        const float g = bn_gy<UP>(gy, y, idx, sp, W, relu);
-        s1 += g;
-        s2 += g * (x[idx] - mean) * istd;
-    }
+    bn_for_each<BnGrad>(
+        BnWalk<UP>(N, C, S, W, c, split, blockIdx.y, threadIdx.x),
+        [&](const BnWalk<UP>& k) { return bn_grad_load<UP>(gy, x, y, nullptr, k, relu); },
+        [&](const BnGrad& e) {
+            BN_NO_CONTRACT
+            const float g = bn_grad<UP>(e, relu);
+            s1 += g;
+            s2 += g * (e.xv - mean) * istd;
+        });
     s1 = block_sum(s1, red);
     s2 = block_sum(s2, red);
     if (threadIdx.x == 0) {
@@ -443,6 +581,21 @@ __global__ void bn_bwd_apply_k(const float* gy, const float* x, const float* y, 
         gx[i] = gamma[c] * istd * (g - ws[c] * invcnt - xh * ws[C + c] * invcnt);
     }
 }
+// what an element of the forward apply passes loads, and its store: BN -> ReLU -> Upsample(2) of an UpBlock in one pass
+// writes the two adjacent copies of each of the two rows as one 8-byte store (o and 2 * W are even)
+struct BnIn {
+    float xv;
+    size_t o;                  // where the result goes (UP: its top-left copy)
+    float tg, tb;              // (the conditional twin's table entries)
+};
+template <bool UP>
+__device__ __forceinline__ void bn_put(float* y, size_t o, int W, float v) {
+    if (UP) {
+        const bn_f2 vv = {v, v};
+        *(bn_f2u*)(y + o) = vv;
+        *(bn_f2u*)(y + o + 2 * (size_t)W) = vv;
+    } else y[o] = v;
+}
 // Fused second passes: every workgroup (channel c, slice y) first merges the channel's partial statistics itself — a
 // short serial Chan merge / sum, identical in every workgroup of the channel — and then normalises its slice; the
 // y == 0 workgroup also publishes the merged values (stats, running stats / dgamma, dbeta). No `final` launch.
@@ -452,6 +605,10 @@ __global__ __launch_bounds__(256) void bn_apply_merge_k(const float* x, const fl
                                                         int N, int C, long S, float momentum, float eps, int relu,
                                                         long long* batches_tracked, int W) {
     const int c = blockIdx.x;
+    BnWalk<UP> wk(N, C, S, W, c, gridDim.y, blockIdx.y, threadIdx.x);
+    const auto load = [&](const BnWalk<UP>& k) { return BnIn{x[k.idx], UP ? k.up() : k.idx, 0.f, 0.f}; };
+    BnIn first[BN_UNROLL];
+    bn_first(first, wk, load);                       // (in flight while the partials are merged)
     if (batches_tracked && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) *batches_tracked += 1;     // nn.BatchNorm's step counter
     float n = 0.f, mean = 0.f, m2 = 0.f;
     for (int k = 0; k < split; ++k) {
@@ -475,22 +632,11 @@ __global__ __launch_bounds__(256) void bn_apply_merge_k(const float* x, const fl
         }
     }
     const float sc = istd * gamma[c], sh = beta[c];
-    const long total = (long)N * S;
-    const long per = (total + gridDim.y - 1) / gridDim.y;
-    const long e0 = (long)blockIdx.y * per;
-    long e1 = e0 + per;
-    if (e1 > total) e1 = total;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
-        const long nn = e / S, sp = e - nn * S;
-        const size_t idx = ((size_t)nn * C + c) * S + sp;
-        float v = (x[idx] - mean) * sc + sh;
+    bn_rest(first, wk, load, [&](const BnIn& e) {
+        float v = BN_FMA(e.xv - mean, sc, sh);                   // (x - mean) * sc + sh
         v = relu ? fmaxf(v, 0.f) : v;
-        if (UP) {                                        // BN -> ReLU -> Upsample(2) of an UpBlock in one pass
-            const long h = sp / W, w = sp - h * W;
-            float* q = y + (idx - sp) * 4 + (size_t)(2 * h) * (2 * W) + 2 * w;
-            q[0] = v; q[1] = v; q[2 * W] = v; q[2 * W + 1] = v;
-        } else y[idx] = v;
-    }
+        bn_put<UP>(y, e.o, W, v);
+    });
 }
 template <bool UP>
 __global__ __launch_bounds__(256) void bn_bwd_apply_merge_k(const float* gy, const float* x, const float* y, const float* stats,
@@ -499,25 +645,23 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_merge_k(const float* gy, con
                                                             const float* __restrict__ add = nullptr) {
     // add: the gradient the input received from its OTHER consumers (t2v_bn_train_bwd_add): summed in here, no add launch
     const int c = blockIdx.x;
+    BnWalk<UP> wk(N, C, S, W, c, gridDim.y, blockIdx.y, threadIdx.x);
+    const auto load = [&](const BnWalk<UP>& k) { return bn_grad_load<UP>(gy, x, y, add, k, relu); };
+    BnGrad first[BN_UNROLL];
+    bn_first(first, wk, load);                       // (in flight while the partials are merged)
     float s1 = 0.f, s2 = 0.f;
     for (int k = 0; k < split; ++k) { s1 += part[((size_t)c * split + k) * 2]; s2 += part[((size_t)c * split + k) * 2 + 1]; }
     if (blockIdx.y == 0 && threadIdx.x == 0) { gbeta[c] = s1; ggamma[c] = s2; }
     const float mean = stats[c], istd = stats[C + c];
     const float invcnt = 1.f / (float)((long)N * S);
     const float k0 = gamma[c] * istd, a1 = s1 * invcnt, a2 = s2 * invcnt;
-    const long total = (long)N * S;
-    const long per = (total + gridDim.y - 1) / gridDim.y;
-    const long e0 = (long)blockIdx.y * per;
-    long e1 = e0 + per;
-    if (e1 > total) e1 = total;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
-        const long nn = e / S, sp = e - nn * S;
-        const size_t idx = ((size_t)nn * C + c) * S + sp;
-        const float g = bn_gy<UP>(gy, y, idx, sp, W, relu);
-        const float xh = (x[idx] - mean) * istd;
-        const float v = k0 * (g - a1 - xh * a2);
-        gx[idx] = add ? v + add[idx] : v;
-    }
+    bn_rest(first, wk, load, [&](const BnGrad& e) {
+        BN_NO_CONTRACT
+        const float g = bn_grad<UP>(e, relu);
+        const float xh = (e.xv - mean) * istd;
+        const float v = k0 * BN_FMA(-xh, a2, g - a1);            // k0 * (g - a1 - xh * a2)
+        gx[e.idx] = add ? v + e.add : v;
+    });
 }
 static int bn_slices(int N, int C, long S) {           // workgroups per channel of the fused second passes
     const long total = (long)N * S;
@@ -550,7 +694,7 @@ extern "C" int t2v_bn_plan(int N, int C, int64_t S, int32_t* out) {
 }
 extern "C" int t2v_bn_stats(const float* x, float* stats, float* rm, float* rv, float* ws, int N, int C, int64_t S, float momentum,
                             float eps, void* st) {
-    if (!x || !stats || !ws || N < 1 || C < 1 || S < 1) return T2V_EINVAL;
+    if (!x || !stats || !ws || N < 1 || C < 1 || S < 1 || S > BN_MAX_PLANE) return T2V_EINVAL;
     const int sp = bn_split(N, C, (long)S);
     T2V_LAUNCH(bn_stats_part_k, dim3(C, sp), dim3(256), 0, S_(st), x, ws, N, C, (long)S, sp);
     T2V_LAUNCH(bn_stats_final_k, dim3((C + 255) / 256), dim3(256), 0, S_(st), ws, stats, rm, rv, C, sp, momentum, eps);
@@ -564,7 +708,7 @@ extern "C" int t2v_bn_apply(const float* x, const float* stats, const float* gam
 }
 extern "C" int t2v_bn_bwd(const float* gy, const float* x, const float* y, const float* stats, const float* gamma, float* gx,
                           float* ggamma, float* gbeta, float* ws, int N, int C, int64_t S, int relu, void* st) {
-    if (!gy || !x || !stats || !gamma || !gx || !ggamma || !gbeta || !ws || N < 1 || C < 1 || S < 1) return T2V_EINVAL;
+    if (!gy || !x || !stats || !gamma || !gx || !ggamma || !gbeta || !ws || N < 1 || C < 1 || S < 1 || S > BN_MAX_PLANE) return T2V_EINVAL;
     if (relu && !y) return T2V_EINVAL;
     const int sp = bn_split(N, C, (long)S);
     float* part = ws + 2 * C;
@@ -576,7 +720,7 @@ extern "C" int t2v_bn_bwd(const float* gy, const float* x, const float* y, const
 extern "C" int t2v_bn_train_fwd(const float* x, const float* gamma, const float* beta, float* y, float* stats, float* rm, float* rv,
                                 float* ws, int N, int C, int64_t S, float momentum, float eps, int relu, int64_t* batches_tracked,
                                 void* st) {
-    if (!x || !gamma || !beta || !y || !stats || !ws || N < 1 || C < 1 || S < 1) return T2V_EINVAL;
+    if (!x || !gamma || !beta || !y || !stats || !ws || N < 1 || C < 1 || S < 1 || S > BN_MAX_PLANE) return T2V_EINVAL;
     const int sp = bn_split(N, C, (long)S);
     T2V_LAUNCH(bn_stats_part_k, dim3(C, sp), dim3(256), 0, S_(st), x, ws, N, C, (long)S, sp);
     T2V_LAUNCH(bn_apply_merge_k<false>, dim3(C, bn_slices(N, C, (long)S)), dim3(256), 0, S_(st), x, ws, sp, gamma, beta, y, stats, rm, rv, N,
@@ -590,6 +734,7 @@ extern "C" int t2v_bn_train_fwd_up(const float* x, const float* gamma, const flo
                                    int64_t* batches_tracked, void* st) {
     if (!x || !gamma || !beta || !y || !stats || !ws || N < 1 || C < 1 || H < 1 || W < 1) return T2V_EINVAL;
     const long S = (long)H * W;
+    if (S > BN_MAX_PLANE) return T2V_EINVAL;
     const int sp = bn_split(N, C, S);
     T2V_LAUNCH(bn_stats_part_k, dim3(C, sp), dim3(256), 0, S_(st), x, ws, N, C, S, sp);
     T2V_LAUNCH(bn_apply_merge_k<true>, dim3(C, bn_slices(N, C, S)), dim3(256), 0, S_(st), x, ws, sp, gamma, beta, y, stats, rm, rv, N,
@@ -602,6 +747,7 @@ extern "C" int t2v_bn_train_bwd_up(const float* gy, const float* x, const float*
     if (!gy || !x || !stats || !gamma || !gx || !ggamma || !gbeta || !ws || N < 1 || C < 1 || H < 1 || W < 1) return T2V_EINVAL;
     if (relu && !y) return T2V_EINVAL;
     const long S = (long)H * W;
+    if (S > BN_MAX_PLANE) return T2V_EINVAL;
     const int sp = bn_split(N, C, S);
     T2V_LAUNCH(bn_bwd_part_k<true>, dim3(C, sp), dim3(256), 0, S_(st), gy, x, y, stats, ws, N, C, S, relu, sp, W);
     T2V_LAUNCH(bn_bwd_apply_merge_k<true>, dim3(C, bn_slices(N, C, S)), dim3(256), 0, S_(st), gy, x, y, stats, gamma, ws, sp, gx,
@@ -610,7 +756,7 @@ extern "C" int t2v_bn_train_bwd_up(const float* gy, const float* x, const float*
 }
 extern "C" int t2v_bn_train_bwd(const float* gy, const float* x, const float* y, const float* stats, const float* gamma, float* gx,
                                 float* ggamma, float* gbeta, float* ws, int N, int C, int64_t S, int relu, void* st) {
-    if (!gy || !x || !stats || !gamma || !gx || !ggamma || !gbeta || !ws || N < 1 || C < 1 || S < 1) return T2V_EINVAL;
+    if (!gy || !x || !stats || !gamma || !gx || !ggamma || !gbeta || !ws || N < 1 || C < 1 || S < 1 || S > BN_MAX_PLANE) return T2V_EINVAL;
     if (relu && !y) return T2V_EINVAL;
     const int sp = bn_split(N, C, (long)S);
     T2V_LAUNCH(bn_bwd_part_k<false>, dim3(C, sp), dim3(256), 0, S_(st), gy, x, y, stats, ws, N, C, (long)S, relu, sp, 1);
@@ -627,6 +773,7 @@ extern "C" int t2v_bn_train_bwd_add(const float* gy, const float* x, const float
     if (!gy || !x || !stats || !gamma || !gx || !ggamma || !gbeta || !ws || N < 1 || C < 1 || H < 1 || W < 1) return T2V_EINVAL;
     if (relu && !y) return T2V_EINVAL;
     const long S = (long)H * W;
+    if (S > BN_MAX_PLANE) return T2V_EINVAL;
     const int sp = bn_split(N, C, S);
     if (up) {
         T2V_LAUNCH(bn_bwd_part_k<true>, dim3(C, sp), dim3(256), 0, S_(st), gy, x, y, stats, ws, N, C, S, relu, sp, W);
@@ -663,12 +810,22 @@ extern "C" int t2v_bn_eval(const float* x, const float* rm, const float* rv, con
 __device__ __forceinline__ const float* cbn_row(const float* tab, long n, int T, int s, int ld, int off, int c) {
     return tab + (size_t)(n / T) * s * ld + off + c;
 }
+__device__ __forceinline__ const float* cbn_row(const float* tab, int n, int T, int s, int ld, int off, int c) {
+    return tab + (size_t)(n / T) * s * ld + off + c;        // (a sample index is an int: a 32-bit division)
+}
 template <bool UP>
 __global__ __launch_bounds__(256) void cbn_apply_merge_k(const float* x, const float* part, int split, const float* gamma,
                                                          const float* beta, const float* tab, int ld, int off, int s, int T,
                                                          float* y, float* stats, float* rmean, float* rvar, int N, int C, long S,
                                                          float momentum, float eps, int relu, long long* batches_tracked, int W) {
     const int c = blockIdx.x;
+    BnWalk<UP> wk(N, C, S, W, c, gridDim.y, blockIdx.y, threadIdx.x);
+    const auto load = [&](const BnWalk<UP>& k) {
+        const float* t = cbn_row(tab, k.n, T, s, ld, off, c);
+        return BnIn{x[k.idx], UP ? k.up() : k.idx, t[0], t[C]};
+    };
+    BnIn first[BN_UNROLL];
+    bn_first(first, wk, load);                       // (in flight while the partials are merged)
     if (batches_tracked && c == 0 && blockIdx.y == 0 && threadIdx.x == 0) *batches_tracked += 1;
     float n = 0.f, mean = 0.f, m2 = 0.f;                 // (the merge of bn_apply_merge_k, statement for statement)
     for (int k = 0; k < split; ++k) {
@@ -692,23 +849,12 @@ __global__ __launch_bounds__(256) void cbn_apply_merge_k(const float* x, const f
         }
     }
     const float g0 = gamma[c], b0 = beta[c];
-    const long total = (long)N * S;
-    const long per = (total + gridDim.y - 1) / gridDim.y;
-    const long e0 = (long)blockIdx.y * per;
-    long e1 = e0 + per;
-    if (e1 > total) e1 = total;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
-        const long nn = e / S, sp = e - nn * S;
-        const size_t idx = ((size_t)nn * C + c) * S + sp;
-        const float* t = cbn_row(tab, nn, T, s, ld, off, c);
-        float v = (x[idx] - mean) * istd * (g0 + t[0]) + (b0 + t[C]);
+    bn_rest(first, wk, load, [&](const BnIn& e) {
+        BN_NO_CONTRACT
+        float v = BN_FMA((e.xv - mean) * istd, g0 + e.tg, b0 + e.tb);            // (x - mean) * istd * (g0 + t[0]) + (b0 + t[C])
         v = relu ? fmaxf(v, 0.f) : v;
-        if (UP) {
-            const long h = sp / W, w = sp - h * W;
-            float* q = y + (idx - sp) * 4 + (size_t)(2 * h) * (2 * W) + 2 * w;
-            q[0] = v; q[1] = v; q[2 * W] = v; q[2 * W + 1] = v;
-        } else y[idx] = v;
-    }
+        bn_put<UP>(y, e.o, W, v);
+    });
 }
 // lanes that share one row of the per-row sums: a power of two within a wave (shuffles only), or the whole workgroup
 static int cbn_row_lanes(long S) {
@@ -753,6 +899,14 @@ __global__ __launch_bounds__(256) void cbn_bwd_apply_merge_k(const float* gy, co
                                                              const float* __restrict__ add) {
     __shared__ float red[16];
     const int c = blockIdx.x;
+    BnWalk<UP> wk(N, C, S, W, c, gridDim.y, blockIdx.y, threadIdx.x);
+    const auto load = [&](const BnWalk<UP>& k) {
+        BnGrad e = bn_grad_load<UP>(gy, x, y, add, k, relu);
+        e.tg = cbn_row(tab, k.n, T, s, ld, off, c)[0];
+        return e;
+    };
+    BnGrad first[BN_UNROLL];
+    bn_first(first, wk, load);                       // (in flight while the partials are merged)
     const float* r = rows + (size_t)c * N * 2;
     const float g0 = gamma[c];
     float sb = 0.f, sg = 0.f, A = 0.f, B = 0.f;
@@ -787,20 +941,14 @@ __global__ __launch_bounds__(256) void cbn_bwd_apply_merge_k(const float* gy, co
     const float mean = stats[c], istd = stats[C + c];
     const float invcnt = 1.f / (float)((long)N * S);
     const float a1 = A * invcnt, a2 = B * invcnt;
-    const long total = (long)N * S;
-    const long per = (total + gridDim.y - 1) / gridDim.y;
-    const long e0 = (long)blockIdx.y * per;
-    long e1 = e0 + per;
-    if (e1 > total) e1 = total;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) {
-        const long nn = e / S, sp = e - nn * S;
-        const size_t idx = ((size_t)nn * C + c) * S + sp;
-        const float g = bn_gy<UP>(gy, y, idx, sp, W, relu);
-        const float xh = (x[idx] - mean) * istd;
-        const float G = g0 + cbn_row(tab, nn, T, s, ld, off, c)[0];
-        const float v = istd * (G * g - a1 - xh * a2);
-        gx[idx] = add ? v + add[idx] : v;
-    }
+    bn_rest(first, wk, load, [&](const BnGrad& e) {
+        BN_NO_CONTRACT
+        const float g = bn_grad<UP>(e, relu);
+        const float xh = (e.xv - mean) * istd;
+        const float G = g0 + e.tg;
+        const float v = istd * BN_FMA(-xh, a2, G * g - a1);      // istd * (G * g - a1 - xh * a2), G * g rounded on its own
+        gx[e.idx] = add ? v + e.add : v;
+    });
 }
 __global__ void cbn_eval_k(const float* x, const float* rm, const float* rv, const float* gamma, const float* beta,
                            const float* tab, int ld, int off, int s, int T, float* y, int N, int C, long S, float eps, int relu) {
@@ -831,6 +979,7 @@ static int cbn_fwd(bool up, const float* x, const float* gamma, const float* bet
                    int relu, int64_t* batches_tracked, void* st) {
     if (!x || !gamma || !beta || !y || !stats || !ws || H < 1 || W < 1 || !cbn_tab_ok(tab, ld, off, s, T, R, N, C)) return T2V_EINVAL;
     const long S = (long)H * W;
+    if (S > BN_MAX_PLANE) return T2V_EINVAL;
     const int sp = bn_split(N, C, S);
     T2V_LAUNCH(bn_stats_part_k, dim3(C, sp), dim3(256), 0, S_(st), x, ws, N, C, S, sp);
     if (up)
@@ -849,6 +998,7 @@ static int cbn_bwd(bool up, const float* gy, const float* x, const float* y, con
         return T2V_EINVAL;
     if (relu && !y) return T2V_EINVAL;
     const long S = (long)H * W;
+    if (S > BN_MAX_PLANE) return T2V_EINVAL;
     const int G = cbn_row_lanes(S);
     const dim3 rgrid(C, (N + 256 / G - 1) / (256 / G)), agrid(C, bn_slices(N, C, S));
     if (up) {
