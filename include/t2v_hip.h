@@ -819,6 +819,45 @@ int t2v_proj_feat(const t2v_proj_member* members, int n, const float* V, int K, 
 int t2v_proj_cond(const t2v_proj_member* members, int n, const float* V, int K, int J, void* stream);
 int t2v_proj_weight(const t2v_proj_member* members, int n, float* W, int K, int J, int accum, void* stream);
 
+/* ---- minibatch standard deviation head of the discriminator (Karras et al. 2018; opt-in, Resnet3D(mbstd=G)) ---------
+ * One definition. f [b, K] = the trunk's spatially summed features of one member, with a segment length seg (b % seg == 0): rows
+ * [i*seg, (i+1)*seg) form a segment, consecutive runs of G rows inside a segment a group; the last group of a segment holds the
+ * remainder (possibly one row); groups never cross a segment boundary. Per group q of n rows:
+ *   mu_k = (1/n) sum_b f_bk    v_k = (1/n) sum_b (f_bk - mu_k)^2    sigma_k = sqrt(v_k + 1e-8)    s_q = (1/K) sum_k sigma_k
+ * and every logit of head h (0 = unconditional, 1 = conditional; w [H] = `mbstd.weight`) of a row b of the group gains w_h s_q.
+ * With a_q = sum_{b in q} sum_h g_h[b] w_h, four roles, each ONE launch for up to T2V_MAX_GROUPS members with their own b and seg:
+ *   t2v_mbstd_fwd     stat[b] = s_q(b);  y_h[b] = (base_h ? base_h[b] : 0) + w_h s_q(b)                  reads f, base; writes y, stat
+ *   t2v_mbstd_feat    out F[b,k] = a_q (f_bk - mu_k) / (n K sigma_k)            (the adjoint of f)        reads f, g; writes out
+ *   t2v_mbstd_second  with Gam = dL/dF:  t_q = sum_bk Gam_bk (f_bk - mu_k) / (n K sigma_k);  stat[b] = t_q(b);  y_h[b] = w_h t_q(b);
+ *                     out[b,k] = (a_q/(nK)) [ (Gam_bk - mean_b Gam_k)/sigma_k - (f_bk - mu_k) sum_b' Gam_b'k (f_b'k - mu_k)/(n sigma_k^3) ]
+ *                                                                                                        reads f, gam, g; writes out, stat, y
+ *   t2v_mbstd_weight  W[h] (+= if accum) sum over members, then rows, of g_h[b] stat[b]   (stat = s: dL/dw; stat = t: its second order)
+ * `members` is a HOST array whose descriptors travel by value in the kernel arguments. Head pointers (g, base, y) beyond H are
+ * ignored; a NULL g_h adds nothing, a NULL y_h, stat or (second) out is not written, a NULL base_h counts as 0. g, base, y and stat
+ * are dense [b] (the [b, 1] logits), f, gam and out dense [b, K]; outputs must not alias inputs. fp32, no atomics, no workspace,
+ * one summation order: the same bits run to run. A single-row group has f - mu == 0 exactly: F, t and out are exact zeros there.
+ * None allocates or synchronises; all can be captured. One workgroup per (member, group); weight is one workgroup.
+ * T2V_EINVAL, before any launch, on members == NULL, w / W == NULL, n outside 1..T2V_MAX_GROUPS, K < 1, H outside
+ * 1..T2V_MBSTD_MAX_HEADS, G outside 2..T2V_MBSTD_MAX_GROUP, a member with b < 1, seg < 1 or b % seg != 0, or without what the role
+ * needs: fwd f and one y_h; feat f, out and one g_h; second f, gam, one of {out, stat, y_h}, and one g_h when out is given;
+ * weight stat and one g_h. */
+#define T2V_MBSTD_MAX_GROUP 16
+#define T2V_MBSTD_MAX_HEADS 2
+typedef struct t2v_mbstd_member {
+    const float* f;                                /* [b, K] */
+    const float* g[T2V_MBSTD_MAX_HEADS];           /* [b] each: dL/dy_h, or NULL */
+    const float* base[T2V_MBSTD_MAX_HEADS];        /* fwd: [b] each, the logits the term is added to, or NULL */
+    const float* gam;                              /* second: [b, K] */
+    float* y[T2V_MBSTD_MAX_HEADS];                 /* fwd, second: [b] each, or NULL */
+    float* stat;                                   /* fwd, second: [b] written (or NULL); weight: [b] read */
+    float* out;                                    /* feat, second: [b, K] */
+    int32_t b, seg;
+} t2v_mbstd_member;
+int t2v_mbstd_fwd(const t2v_mbstd_member* members, int n, const float* w, int H, int K, int G, void* stream);
+int t2v_mbstd_feat(const t2v_mbstd_member* members, int n, const float* w, int H, int K, int G, void* stream);
+int t2v_mbstd_second(const t2v_mbstd_member* members, int n, const float* w, int H, int K, int G, void* stream);
+int t2v_mbstd_weight(const t2v_mbstd_member* members, int n, float* W, int H, int K, int G, int accum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,12 @@ class ProjMember(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class MbstdMember(C.Structure):
+    """t2v_mbstd_member (include/t2v_hip.h)."""
+    _fields_ = [('f', C.c_void_p), ('g', C.c_void_p * 2), ('base', C.c_void_p * 2), ('gam', C.c_void_p), ('y', C.c_void_p * 2),
+                ('stat', C.c_void_p), ('out', C.c_void_p), ('b', C.c_int32), ('seg', C.c_int32)]
+
+
 MAX_GROUPS = 8
 _P = C.c_void_p
 _I = C.c_int
@@ -276,6 +282,10 @@ SIGNATURES = {
     't2v_proj_feat': [_P, _I, _P, _I, _I, _P],
     't2v_proj_cond': [_P, _I, _P, _I, _I, _P],
     't2v_proj_weight': [_P, _I, _P, _I, _I, _I, _P],
+    't2v_mbstd_fwd': [_P, _I, _P, _I, _I, _I, _P],
+    't2v_mbstd_feat': [_P, _I, _P, _I, _I, _I, _P],
+    't2v_mbstd_second': [_P, _I, _P, _I, _I, _I, _P],
+    't2v_mbstd_weight': [_P, _I, _P, _I, _I, _I, _I, _P],
     't2v_prof_begin': [_I],
     't2v_prof_end': [C.POINTER(C.c_double), _I],
     't2v_version': [],

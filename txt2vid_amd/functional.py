@@ -2832,6 +2832,10 @@ from .functional_pool import (pool_conv_ok, pool_conv_group, pool_tmode, PoolCon
 # the projection head of the text-conditioned discriminator (opt-in): functional_proj.py
 from .functional_proj import (proj_rows_group, proj_rows_raw, proj_feat_raw, proj_cond_raw, proj_weight_raw, ProjRowsG, ProjFeatG,     # noqa: E402,F401
                               ProjCondG, ProjWeightG)
+# the minibatch standard deviation head of the discriminator (opt-in): functional_mbstd.py
+from .functional_mbstd import check_group as mbstd_check_group  # noqa: E402,F401
+from .functional_mbstd import (mbstd_group, mbstd_fwd_raw, mbstd_feat_raw, mbstd_second_raw, mbstd_weight_raw, MbstdFwdG, MbstdFeatG,     # noqa: E402,F401
+                               MbstdSecondG, MbstdWeightG)
 
 
 def add_group(as_, bs):

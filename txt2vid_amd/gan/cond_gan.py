@@ -114,9 +114,12 @@ class CondGan(object):
 
     def _discrim_forward_fused(self, discrim, real, fake, real_cond, fake_cond, loss, gp_lambda):
         """The whole D-step forward as ONE lock-step pass over up to 8 tensors that share the trunk: the real
-        and generated clips of each pyramid level as one batch (D has no batch-coupled op) and, when the
-        gradient penalty is on, the interpolated clips x_hat of each level. Same arithmetic as the branchy
-        path above; the GP alphas are drawn from the host generator in the same stream position."""
+        and generated clips of each pyramid level as one batch and, when the gradient penalty is on, the
+        interpolated clips x_hat of each level. Same arithmetic as the branchy path above; the GP alphas are
+        drawn from the host generator in the same stream position. D's only batch-coupled op is the opt-in
+        minibatch standard deviation head (`mbstd`): with it, a real||fake batch of 2b rows goes in with the
+        segment length b, so that its statistic is taken over the real rows and over the generated rows apart,
+        as two separate calls would; the interpolates are one segment each."""
         n = len(real)
         cond = real_cond is not None and fake_cond is not None
         a_dev = [TF.draws.alpha(real[i].size(0), real[i].dim(), real[i].device) for i in range(n)] if gp_lambda > 0 else None
@@ -140,9 +143,10 @@ class CondGan(object):
             conds = [TF.cat_batch(c, c) for c in real_cond]
             if gp_lambda > 0:
                 chs = [TF.lerp_rows(a_dev[i], real_cond[i], fake_cond[i]) for i in range(n)]
-        res = discrim(x=rf + xhs, cond=(conds + chs) if (cond and xhs) else conds, xbar=None)
-        both, gp_res = res[:n], res[n:]
         b = [r.size(0) for r in real]
+        seg_kw = {'segs': b + [t.size(0) for t in xhs]} if getattr(discrim, 'mbstd_on', 0) else {}
+        res = discrim(x=rf + xhs, cond=(conds + chs) if (cond and xhs) else conds, xbar=None, **seg_kw)
+        both, gp_res = res[:n], res[n:]
         u_r, u_f = TF.split_rows_group([o[0] for o in both], b)
         self._observe(discrim, u_r, u_f)
         pred_r, pred_f = u_r, u_f
@@ -320,6 +324,8 @@ class CondGan(object):
             if name in to_load:
                 if hasattr(d, 'refuse_proj_mismatch'):
                     d.refuse_proj_mismatch(to_load[name])          # (before the key matching, which keeps the wanted keys only)
+                if hasattr(d, 'refuse_mbstd_mismatch'):
+                    d.refuse_mbstd_mismatch(to_load[name])
                 d.load_state_dict(_match_keys(to_load[name], d.state_dict().keys()))
         if self.gen_ema is not None:
             # a file without the key (written without --G_ema, or by the reference) leaves the average a copy of the loaded `gen`;

@@ -11,6 +11,32 @@ _PROJ_MISMATCH = ('discriminator checkpoint %s projection head (proj.weight key)
                   'pass the same proj in the --D spec')
 
 
+_MBSTD_MISMATCH = ('discriminator checkpoint %s minibatch standard deviation head (mbstd.weight key) but this discriminator was '
+                   'built with mbstd=%s: pass the same mbstd in the --D spec')
+
+
+class MinibatchStd(nn.Module):
+    """The weight of the minibatch standard deviation head (`Resnet3D(mbstd=G)`, Karras et al. 2018; not in the reference). One
+    definition (functional_mbstd.py): rows [i·seg, (i+1)·seg) of the features f [b, K] form a segment (seg = b unless stated),
+    runs of G consecutive rows inside a segment a group, the last one holding the remainder; per group q of n rows
+    σ_k = sqrt((1/n) Σ_b (f_bk − μ_k)² + 1e-8), s_q = (1/K) Σ_k σ_k, and the logits of the group's rows gain w_u·s_q
+    (unconditional) and w_c·s_q (conditional). `weight` = w = (w_u, w_c), or (w_u,) without a sentence code: StyleGAN's extra
+    feature column in front of the linear heads. w starts as zeros and `init()` walks past this class without drawing, so a
+    fresh model computes what the plain one computes and every other layer's host draws are unchanged; dL/dw is not zero
+    there, so training moves it. Not an nn.Linear: `--D_sn` leaves w alone."""
+
+    def __init__(self, group, heads):
+        super().__init__()
+        self.group = TF.mbstd_check_group(group)
+        self.weight = nn.Parameter(torch.zeros(int(heads)))
+
+    def forward(self, feats, us, cs, segs=None):
+        """(us, cs) with the term added, one launch for every member and both heads; a head given as None is not computed."""
+        bases = [us, cs][:self.weight.numel()]
+        res = TF.mbstd_group(self.weight, self.group, feats, bases, segs)
+        return res[0], (res[1] if len(res) > 1 else cs)
+
+
 class CondProjection(nn.Module):
     """The weight of the projection head (`Resnet3D(proj=True)`, Miyato & Koyama 2018; not in the reference): `weight` = V
     [in_ch, cond_dim] adds featᵀ V s to the conditional logit (functional_proj.py). V starts as zeros and `init()` walks past
@@ -29,12 +55,16 @@ class CondProjection(nn.Module):
 class Resnet3D(nn.Module):
 
     def __init__(self, num_channels=1, mid_ch=64, which_conv=None, which_pool=None, cond_dim=0, num_down_blocks=4,
-                 wide=False, with_attn=True, proj=False):
+                 wide=False, with_attn=True, proj=False, mbstd=0):
         super().__init__()
         # proj: the conditional logit gains the bilinear term featᵀ V s of a projection discriminator (functional_proj.py; not in
         # the reference, off by default). proj = False builds exactly the reference's module.
         if proj and cond_dim < 1:
             raise ValueError('proj (projection head) needs a sentence code (cond_dim > 0): it cannot run with --dont_use_sent')
+        # mbstd: group size G of the minibatch standard deviation head (MinibatchStd above; not in the reference); 0 = off builds
+        # exactly the reference's module.
+        if mbstd != 0:
+            TF.mbstd_check_group(mbstd)
         which_conv = which_conv or Conv3d
         which_pool = which_pool or AvgPool3d
         self.activation = ReLU()
@@ -54,15 +84,18 @@ class Resnet3D(nn.Module):
             self.fc = Linear(in_ch + cond_dim, 1)
         if proj:
             self.proj = CondProjection(in_ch, cond_dim)           # registered after fc: one trailing state-dict key
+        if mbstd:
+            self.mbstd = MinibatchStd(mbstd, 2 if cond_dim > 0 else 1)        # registered last: one trailing state-dict key
 
     def groupable(self):
         m = self.res_block.inner_module
         return isinstance(m[0], Conv3d) and isinstance(m[2], Conv3d) and all(
             isinstance(d, (DownBlock, Attention3d)) for d in self.down)
 
-    def forward_levels(self, xs, conds=None):
+    def forward_levels(self, xs, conds=None, segs=None):
         """All pyramid levels through the shared trunk in lock-step: every convolution layer is ONE grouped
-        launch over the levels (same results as level-by-level `forward`, resnet3d.py:38-57)."""
+        launch over the levels (same results as level-by-level `forward`, resnet3d.py:38-57). segs (mbstd only): the segment
+        length of every member for the minibatch statistic (default: its batch size) — a real‖fake member of 2b rows takes b."""
         m = self.res_block.inner_module
         idm = self.res_block.identity_map
         # the clips feed the residual path and the skip path: a grouped fork sums their two gradients (generator step, gradient
@@ -107,6 +140,15 @@ class Resnet3D(nn.Module):
                 hs = nonlocal_levels(d, hs)
         feats = TF.sum_spatial_group(hs)                                      # torch.sum(x, [2,3,4]) of every level: one launch
         f_u = f_c = feats
+        mb = getattr(self, 'mbstd', None)
+        f_m = None
+        if mb is not None:
+            # one more consumer of the features: the minibatch statistic (a grouped fork sums its gradient in one launch)
+            f_m, rest = TF.fork_group(feats)
+            if conds is None:
+                f_u = rest
+            else:
+                feats = rest
         if conds is not None:
             # three consumers (unconditional head, conditional head, the caller's mismatched-caption head on the returned features):
             # two grouped forks sum their gradients for all levels in two launches instead of two ATen adds per level
@@ -114,16 +156,34 @@ class Resnet3D(nn.Module):
             f_c, feats = TF.fork_group(rest)
         w5 = self.fc_uncond.weight.view(self.fc_uncond.weight.shape + (1, 1, 1))
         us = TF.conv_group([f.view(f.shape + (1, 1, 1)) for f in f_u], w5, self.fc_uncond.bias)   # all heads: one launch
-        cs = self.cond_heads(f_c, conds) if conds is not None else [None] * len(feats)
-        return [(u.view(u.shape[0], u.shape[1]), c, feat) for feat, u, c in zip(feats, us, cs)]
+        us = [u.view(u.shape[0], u.shape[1]) for u in us]
+        if mb is None:
+            cs = self.cond_heads(f_c, conds) if conds is not None else [None] * len(feats)
+        elif conds is None:
+            us, cs = mb(f_m, us, None, segs)[0], [None] * len(feats)
+        else:
+            us, cs = mb(f_m, us, self._cond_heads_plain(f_c, conds), segs)         # both heads of every member: one launch
+        return [(u, c, feat) for feat, u, c in zip(feats, us, cs)]
 
-    def cond_heads(self, feats, conds):
+    def cond_heads(self, feats, conds, segs=None):
         """`self.fc(torch.cat((features, cond), 1))` (resnet3d.py:53-55) for several levels / members at once: one launch for
-        all concatenations, one for all heads (instead of two copies + one linear per member)."""
+        all concatenations, one for all heads (instead of two copies + one linear per member). With mbstd, plus w_c·s of every
+        member's own rows (segs: a segment length per member, default its row count)."""
+        mb = getattr(self, 'mbstd', None)
+        if mb is None:
+            return self._cond_heads_plain(feats, conds)
+        feats, conds = list(feats), list(conds)
+        if not (1 <= len(feats) <= TF.MAX_GROUPS) or not feats[0].is_cuda:
+            return [self._cond_head(f, c, None if segs is None else segs[i]) for i, (f, c) in enumerate(zip(feats, conds))]
+        feats, feats_m = TF.fork_group(feats)
+        return mb(feats_m, None, self._cond_heads_plain(feats, conds), segs)[1]
+
+    def _cond_heads_plain(self, feats, conds):
+        """The conditional heads without the minibatch statistic."""
         feats, conds = list(feats), list(conds)
         proj = getattr(self, 'proj', None)
         if not (1 <= len(feats) <= TF.MAX_GROUPS) or not feats[0].is_cuda:
-            return [self._cond_head(f, c) for f, c in zip(feats, conds)]
+            return [self._cond_head_plain(f, c) for f, c in zip(feats, conds)]
         feats_p, conds_p = feats, conds
         if proj is not None:
             # features and sentence codes feed the existing head AND the projection term: grouped forks sum the two gradients of
@@ -136,8 +196,15 @@ class Resnet3D(nn.Module):
         cs = [c.view(c.shape[0], c.shape[1]) for c in cs]
         return cs if proj is None else proj(feats_p, conds_p, cs)
 
-    def _cond_head(self, feat, cond):
+    def _cond_head(self, feat, cond, seg=None):
         """The conditional head of one member: the same values as `cond_heads` on a list of one."""
+        mb = getattr(self, 'mbstd', None)
+        if mb is None:
+            return self._cond_head_plain(feat, cond)
+        (f,), (f_m,) = TF.fork_group([feat])
+        return mb([f_m], None, [self._cond_head_plain(f, cond)], None if seg is None else [seg])[1][0]
+
+    def _cond_head_plain(self, feat, cond):
         proj = getattr(self, 'proj', None)
         if proj is None:
             return self.fc(TF.cat_features(feat, cond))
@@ -150,13 +217,20 @@ class Resnet3D(nn.Module):
         has = 'proj.weight' in state_dict
         if has != hasattr(self, 'proj'):
             raise ValueError(_PROJ_MISMATCH % ('has' if has else 'has no', hasattr(self, 'proj')))
+        has = 'mbstd.weight' in state_dict
+        if has != hasattr(self, 'mbstd'):
+            raise ValueError(_MBSTD_MISMATCH % ('has' if has else 'has no', self.mbstd.group if hasattr(self, 'mbstd') else 0))
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
-    def forward(self, x=None, cond=None, xbar=None, computed_features=None):
+    def forward(self, x=None, cond=None, xbar=None, computed_features=None, seg=None):
+        """seg (mbstd only): the segment length of the rows for the minibatch statistic (default: all rows are one segment)."""
         uncond = None
+        mb = getattr(self, 'mbstd', None)
         if computed_features is None and x is not None and self.groupable():
             # one tensor = a group of one: the same launches and the same fused adjoints (forked inputs, conv1 + skip in one
             # Function, grouped non-local block) as the multi-level pass
+            if mb is not None:
+                return self.forward_levels([x], [cond] if cond is not None else None, None if seg is None else [seg])[0]
             return self.forward_levels([x], [cond] if cond is not None else None)[0]
         if computed_features is not None:
             x = computed_features
@@ -166,8 +240,12 @@ class Resnet3D(nn.Module):
                 x = d(x)
             x = TF.sum_spatial(x)                           # torch.sum(x, [2,3,4])  (resnet3d.py:48)
             computed_features = x
-            uncond = self.fc_uncond(x)
+            if mb is None:
+                uncond = self.fc_uncond(x)
+            else:
+                (f_u,), (f_m,) = TF.fork_group([x])
+                uncond = mb([f_m], [self.fc_uncond(f_u)], None, None if seg is None else [seg])[0][0]
         if cond is not None:
-            c = self._cond_head(x, cond)
+            c = self._cond_head(x, cond, seg) if mb is not None else self._cond_head(x, cond)
             return uncond, c, computed_features
         return uncond, None, computed_features
