@@ -91,11 +91,15 @@ typedef struct {
     float* dst;           /* packed matrix base */
     int32_t Cout, Cin, T, ntaps, mode, dst_rows, dst_cols, row_off, col_off;
     int32_t block_begin;  /* first workgroup of this job */
-    int32_t bx, by;       /* ceil(Cin/32), ceil(Cout/32); the job owns bx*by*ntaps workgroups */
+    int32_t bx, by;       /* ceil(Cin/32), ceil(Cout/32); the job owns bx*by*t2v_pack_job_groups(T, ntaps, mode) workgroups */
     int8_t taps[T2V_MAX_TAPS];
     int8_t pad_[5];
 } t2v_pack_job;
 int t2v_pack_job_bytes(void);
+/* Third factor of a job's workgroup count (host arithmetic, nothing is launched): a [Cout][Cin][T] source with T > 9 is read in
+ * groups of 9 consecutive kernel positions, one workgroup per (32 x 32 tile, group) whichever taps are listed; a tap-major
+ * source (mode | 8) or T <= 9 takes one workgroup per (tile, listed tap). */
+int t2v_pack_job_groups(int T, int ntaps, int mode);
 int t2v_pack_multi(const void* table /* device t2v_pack_job[njobs] */, int njobs, int total_blocks, void* stream);
 
 /* y[N,Cout,D,H,W] = conv(x[N,Cin,D,H,W], wp) (+bias).  Implicit GEMM on v_mfma_f32_32x32x2_f32:

@@ -133,6 +133,7 @@ SIGNATURES = {
     't2v_pack_weight': [_P, _P, _I, _I, _I, _I3, _I, _I, _P],
     't2v_pack_job_bytes': [],
     't2v_pack_multi': [_P, _I, _I, _P],
+    't2v_pack_job_groups': [_I, _I, _I],
     't2v_pack_weight_into': [_P, _P, _I, _I, _I, _I3, _I, _I, _I, _I, _I, _I, _P],
     't2v_conv_fwd': [_P, _P, _P, _P, _P, _G, _I, _P],
     't2v_conv_fwd_ws_floats': [_G],

@@ -157,39 +157,147 @@ extern "C" int t2v_prof_end(double* out, int nkinds) {
 // ------------------------------------------------------------------------------------------------
 struct TapList { int32_t n; int32_t t[T2V_MAX_TAPS]; };
 
-__global__ __launch_bounds__(256) void pack_weight_kernel(const float* __restrict__ w, float* __restrict__ wp,
+// ---- the tile body of every pack entry point (single tensor, bf16 single tensor, multi-tensor).
+// A workgroup owns one 32 x 32 (co, ci) tile and a third index z:
+//   * sources stored [co][ci][t] with T > PK_TG (GROUPED; the 3x3x3 weights): z = a group of PK_TG consecutive kernel positions
+//     of the SOURCE. The workgroup reads its 32 co rows with the lanes running along memory (per row and half tile the 16 ci x nt
+//     positions of the group: runs of nt floats every T floats, so a fetched 128-byte line is used nt/T of the way instead of 1/T
+//     and is fetched by T/nt workgroups instead of T), keeps them in LDS as [co][ci][t] and writes every LISTED tap that falls
+//     into its group; the two 16-wide ci halves of the tile go through the same 18 KB of LDS one after the other. A group no
+//     listed tap falls into costs one pass over the tap list; a group with ONE listed tap reads that tap alone (below).
+//   * tap-major sources (mode | 8) and T <= PK_TG: z = index into the tap list, one tap's 32 x 32 plane per workgroup (measured:
+//     for T = 9 the strided source reads of this form cost nothing against T = 1, and its small workgroups fill the chip better).
+// mode & 7: 0 dst[j][ci][co] fp32, 1 dst[j][co][ci] mirrored fp32, 2 dst[j][co][ci] bf16, 3 dst[j][ci][co] mirrored bf16.
+#define PK_TG 9
+#define PK_CW 16                       // ci columns per pass of the grouped path
+#define PK_PITCH (PK_CW * PK_TG + 1)   // LDS floats per co row: odd (lanes along co: stride PK_PITCH, lanes along ci: stride nt)
+__host__ __device__ inline int pack_job_groups(int T, int ntaps, int mode) {
+    return ((mode & 8) || T <= PK_TG) ? ntaps : (T + PK_TG - 1) / PK_TG;
+}
+extern "C" int t2v_pack_job_groups(int T, int ntaps, int mode) {
+    if (T < 1 || ntaps < 1) return T2V_EINVAL;
+    return pack_job_groups(T, ntaps, mode);
+}
+
+// pointers that come out of a job record are generic to the compiler: it would access them with flat_load / flat_store, whose
+// completion it can only await with vmcnt(0) + lgkmcnt(0) (every load in flight, not the oldest). They are device global memory:
+// say so.
+#define T2V_GLOBAL __attribute__((address_space(1)))
+__device__ __forceinline__ float gload(const float* p) { return *(const T2V_GLOBAL float*)p; }
+__device__ __forceinline__ void pack_store(void* __restrict__ dst, size_t o, float v, bool b16) {
+    if (b16) ((T2V_GLOBAL __bf16*)dst)[o] = (__bf16)v; else ((T2V_GLOBAL float*)dst)[o] = v;
+}
+
+// the 32 x PK_CW x nt block [co][ci][t0 + tt] of a [co][ci][t] source -> lds[co_l * PK_PITCH + ci_l * nt + tt]; NT = 0: nt at run time
+template <int NT>
+__device__ __forceinline__ void pack_group_read(float* __restrict__ lds, const float* __restrict__ w, int Cout, int Cin, int T,
+                                                int co0, int ci0, int t0, int nt_rt) {
+    const int nt = NT ? NT : nt_rt;
+    const int per_row = PK_CW * nt, total = 32 * per_row;
+    const float* __restrict__ base = w + ((size_t)co0 * Cin + ci0) * T + t0;      // wave-uniform base + a 32-bit lane offset
+    const int rmax = Cout - 1 - co0, cmax = Cin - 1 - ci0;
+#pragma unroll 3
+    for (int e = threadIdx.x; e < total; e += 256) {
+        const int r = e / per_row, q = e - r * per_row;       // q = ci_l * nt + tt runs along memory
+        const int ci_l = q / nt, tt = q - ci_l * nt;
+        // (positions past the weight's edge re-read its last row / column: every load is issued unconditionally, so that the
+        // compiler keeps the unrolled loads in flight together; what they leave in LDS is never written out)
+        lds[r * PK_PITCH + q] = gload(base + (unsigned)((min(r, rmax) * Cin + min(ci_l, cmax)) * T + tt));
+    }
+}
+
+template <class TapT>
+__device__ __forceinline__ void pack_tile(float* __restrict__ lds, const float* __restrict__ w, void* __restrict__ dst, const int Cout,
+                                          const int Cin, const int T, const int ntaps, const TapT* taps, const int mode,
+                                          const int dst_rows, const int dst_cols, const int row_off, const int col_off, const int bxi,
+                                          const int byi, const int z) {
+    const int jm = mode & 7;
+    const bool src_tm = mode & 8;
+    const bool mirror = jm == 1 || jm == 3, transpose = jm == 0 || jm == 3, b16 = jm >= 2;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+    const int co0 = byi * 32, ci0 = bxi * 32;
+    int j1 = z;                                    // the one tap of the single-tap path
+    if (!src_tm && T > PK_TG) {
+        const int t0 = z * PK_TG, nt = T - t0 < PK_TG ? T - t0 : PK_TG;
+        int nl = 0;
+        for (int j = 0; j < ntaps; ++j) {
+            const int tj = __builtin_amdgcn_readfirstlane((int)taps[j]);
+            const int tt = (mirror ? T - 1 - tj : tj) - t0;
+            if (tt >= 0 && tt < nt) { ++nl; j1 = j; }
+        }
+        if (nl == 0) return;
+        if (nl > 1) {
+            for (int cih = ci0; cih < ci0 + 32 && cih < Cin; cih += PK_CW) {       // the tile's two ci halves
+                if (cih != ci0) __syncthreads();
+                if (nt == 9) pack_group_read<9>(lds, w, Cout, Cin, T, co0, cih, t0, nt);
+                else pack_group_read<0>(lds, w, Cout, Cin, T, co0, cih, t0, nt);
+                __syncthreads();
+                for (int j = 0; j < ntaps; ++j) {
+                    const int tj = __builtin_amdgcn_readfirstlane((int)taps[j]);
+                    const int tt = (mirror ? T - 1 - tj : tj) - t0;
+                    if (tt < 0 || tt >= nt) continue;
+                    const size_t ob = (size_t)j * dst_rows + row_off;
+                    if (transpose) {               // rows ci (16), lanes co: 128-byte runs
+#pragma unroll
+                        for (int r = ty; r < PK_CW; r += 8) {
+                            const int ci = cih + r, co = co0 + tx;
+                            if (ci < Cin && co < Cout) pack_store(dst, (ob + ci) * dst_cols + col_off + co, lds[tx * PK_PITCH + r * nt + tt], b16);
+                        }
+                    } else {                       // rows co, 16 lanes along ci (64-byte runs; the other half follows), two rows per 32 lanes
+#pragma unroll
+                        for (int r = ty * 2 + (tx >> 4); r < 32; r += 16) {
+                            const int co = co0 + r, cl = tx & 15, ci = cih + cl;
+                            if (co < Cout && ci < Cin) pack_store(dst, (ob + co) * dst_cols + col_off + ci, lds[r * PK_PITCH + cl * nt + tt], b16);
+                        }
+                    }
+                }
+            }
+            return;
+        }
+    }
+    // one tap: tile[32][33] transpose through LDS where the destination's inner index is co
+    const int j = j1;
+    const int tj = __builtin_amdgcn_readfirstlane((int)taps[j]);
+    const int t = mirror ? (T - 1 - tj) : tj;
+    const size_t sco = src_tm ? (size_t)Cin : (size_t)Cin * T, sci = src_tm ? 1 : (size_t)T;
+    const size_t st = src_tm ? (size_t)t * Cout * Cin : (size_t)t;
+    const size_t ob = (size_t)j * dst_rows + row_off;
+    if (transpose) {
+#pragma unroll
+        for (int r = ty; r < 32; r += 8) {          // read rows co, lanes ci
+            const int co = min(co0 + r, Cout - 1), ci = min(ci0 + tx, Cin - 1);
+            lds[r * 33 + tx] = gload(w + co * sco + ci * sci + st);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = ty; r < 32; r += 8) {          // write rows ci, lanes co
+            const int ci = ci0 + r, co = co0 + tx;
+            if (ci < Cin && co < Cout) pack_store(dst, (ob + ci) * dst_cols + col_off + co, lds[tx * 33 + r], b16);
+        }
+    } else {
+#pragma unroll
+        for (int r = ty; r < 32; r += 8) {
+            const int co = co0 + r, ci = ci0 + tx;
+            if (co < Cout && ci < Cin) pack_store(dst, (ob + co) * dst_cols + col_off + ci, gload(w + co * sco + ci * sci + st), b16);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void pack_weight_kernel(const float* __restrict__ w, void* __restrict__ wp,
                                                           int Cout, int Cin, int T, TapList taps, int mode, int dst_rows,
                                                           int dst_cols, int row_off, int col_off) {
     // mode 0: wp[j][row_off + ci][col_off + co] = w[co][ci][t_j]      (per-tap matrix [dst_rows][dst_cols], inner = co)
     // mode 1: wp[j][row_off + co][col_off + ci] = w[co][ci][T-1-t_j]  (inner = ci)
     // dst_rows / dst_cols > the weight's own extents let several weights share one packed matrix (the four
     // ConvLSTM gates become one GEMM). 32x32 tile transpose of the (co,ci) plane through LDS for mode 0.
-    __shared__ float tile[32][33];
-    const int j = blockIdx.z;
-    const bool src_tm = mode & 8;                   // source stored tap-major: w[t][co][ci]
-    mode &= 7;
-    const int t = mode ? (T - 1 - taps.t[j]) : taps.t[j];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    const int co0 = blockIdx.y * 32, ci0 = blockIdx.x * 32;
-    const size_t sco = src_tm ? (size_t)Cin : (size_t)Cin * T, sci = src_tm ? 1 : (size_t)T;
-    const size_t st = src_tm ? (size_t)t * Cout * Cin : (size_t)t;
-    if (mode == 0) {
-        for (int r = ty; r < 32; r += 8) {          // read rows co, lanes ci (stride T)
-            int co = co0 + r, ci = ci0 + tx;
-            tile[r][tx] = (co < Cout && ci < Cin) ? w[co * sco + ci * sci + st] : 0.f;
-        }
-        __syncthreads();
-        for (int r = ty; r < 32; r += 8) {          // write rows ci, lanes co
-            int ci = ci0 + r, co = co0 + tx;
-            if (ci < Cin && co < Cout) wp[((size_t)j * dst_rows + row_off + ci) * dst_cols + col_off + co] = tile[tx][r];
-        }
-    } else {
-        for (int r = ty; r < 32; r += 8) {
-            int co = co0 + r, ci = ci0 + tx;
-            if (co < Cout && ci < Cin)
-                wp[((size_t)j * dst_rows + row_off + co) * dst_cols + col_off + ci] = w[co * sco + ci * sci + st];
-        }
-    }
+    // mode 2 / 3: the bf16-compute layouts (t2v_pack_weight_bf16 mode 0 / 1), see pack_tile
+    __shared__ float lds[32 * PK_PITCH];
+    __shared__ int s_taps[T2V_MAX_TAPS];
+    if ((int)threadIdx.x < taps.n) s_taps[threadIdx.x] = taps.t[threadIdx.x];
+    __syncthreads();
+    const int bx = (Cin + 31) / 32, by = (Cout + 31) / 32;
+    const int b = blockIdx.x;
+    pack_tile(lds, w, wp, Cout, Cin, T, taps.n, s_taps, mode, dst_rows, dst_cols, row_off, col_off, b % bx, (b / bx) % by, b / (bx * by));
 }
 
 extern "C" int t2v_pack_weight_into(const float* w, float* wp, int Cout, int Cin, int T, const int32_t* taps, int ntaps,
@@ -204,9 +312,10 @@ extern "C" int t2v_pack_weight_into(const float* w, float* wp, int Cout, int Cin
         if (taps[i] < 0 || taps[i] >= T) return T2V_EINVAL;
         tl.t[i] = taps[i];
     }
-    dim3 grid((Cin + 31) / 32, (Cout + 31) / 32, ntaps);
-    T2V_LAUNCH(pack_weight_kernel, grid, dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, T, tl, mode, dst_rows, dst_cols,
-               row_off, col_off);
+    const long nb = (long)((Cin + 31) / 32) * ((Cout + 31) / 32) * pack_job_groups(T, ntaps, mode);
+    if (nb > 0x7fffffffL) return T2V_EINVAL;
+    T2V_LAUNCH(pack_weight_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, (void*)wp, Cout, Cin, T, tl, mode, dst_rows,
+               dst_cols, row_off, col_off);
     return launch_status();
 }
 
@@ -228,11 +337,10 @@ struct PackJob {
     int8_t pad_[5];
 };
 
-// (round 3: a form where one workgroup reads its tile's rows as contiguous runs of (tile ci) x T floats and writes all live taps from
-// LDS — no T-fold line re-reads — was measured and dropped: 141 vs 125 us per launch; the re-reads hit L2 and the 23 000 small
-// workgroups of this form keep more bytes in flight.)
+// (round 3: a form where one workgroup kept its tile's rows for ALL T taps in LDS (110 KB at T = 27: one workgroup per CU) was
+// measured and dropped, 141 vs 125 us per launch. pack_tile keeps groups of PK_TG taps instead: 37 KB, four workgroups per CU.)
 __global__ __launch_bounds__(256) void pack_multi_kernel(const PackJob* __restrict__ table, int njobs) {
-    __shared__ float tile[32][33];
+    __shared__ float lds[32 * PK_PITCH];
     __shared__ PackJob job;
     // binary search: last job with block_begin <= blockIdx.x
     if (threadIdx.x == 0) {
@@ -244,50 +352,18 @@ __global__ __launch_bounds__(256) void pack_multi_kernel(const PackJob* __restri
         job = table[lo];
     }
     __syncthreads();
-    const int b = (int)blockIdx.x - job.block_begin;
-    const int bxi = b % job.bx, byi = (b / job.bx) % job.by, j = b / (job.bx * job.by);
-    const int Cout = job.Cout, Cin = job.Cin, T = job.T;
-    // mode 0 / 1: fp32 forward / mirrored data-gradient layouts (see t2v_pack_weight); mode 2 / 3: the bf16-compute layouts
-    // (t2v_pack_weight_bf16 mode 0 / 1): 2 = dst[j][co][ci], 3 = dst[j][ci][co] mirrored, both bf16
-    const int jm = job.mode & 7;
-    const bool src_tm = job.mode & 8;               // source stored tap-major: w[t][co][ci]
-    const bool mirror = jm == 1 || jm == 3, transpose = jm == 0 || jm == 3, b16 = jm >= 2;
-    const int t = mirror ? (T - 1 - job.taps[j]) : job.taps[j];
-    const size_t sco = src_tm ? (size_t)Cin : (size_t)Cin * T, sci = src_tm ? 1 : (size_t)T;
-    const size_t st = src_tm ? (size_t)t * Cout * Cin : (size_t)t;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int co0 = byi * 32, ci0 = bxi * 32;
-    const float* __restrict__ w = job.src;
-    float* __restrict__ wp = job.dst;
-    __bf16* __restrict__ wpb = reinterpret_cast<__bf16*>(job.dst);
-    if (transpose) {
-        for (int r = ty; r < 32; r += 8) {
-            int co = co0 + r, ci = ci0 + tx;
-            tile[r][tx] = (co < Cout && ci < Cin) ? w[co * sco + ci * sci + st] : 0.f;
-        }
-        __syncthreads();
-        for (int r = ty; r < 32; r += 8) {
-            int ci = ci0 + r, co = co0 + tx;
-            if (ci < Cin && co < Cout) {
-                const size_t o = ((size_t)j * job.dst_rows + job.row_off + ci) * job.dst_cols + job.col_off + co;
-                if (b16) wpb[o] = (__bf16)tile[tx][r]; else wp[o] = tile[tx][r];
-            }
-        }
-    } else {
-        for (int r = ty; r < 32; r += 8) {
-            int co = co0 + r, ci = ci0 + tx;
-            if (co < Cout && ci < Cin) {
-                const size_t o = ((size_t)j * job.dst_rows + job.row_off + co) * job.dst_cols + job.col_off + ci;
-                const float v = w[co * sco + ci * sci + st];
-                if (b16) wpb[o] = (__bf16)v; else wp[o] = v;
-            }
-        }
-    }
+    const int b = (int)blockIdx.x - __builtin_amdgcn_readfirstlane(job.block_begin);
+    const int bx = __builtin_amdgcn_readfirstlane(job.bx), by = __builtin_amdgcn_readfirstlane(job.by);      // (wave-uniform: scalar branches)
+    const int bxi = b % bx, byi = (b / bx) % by, z = b / (bx * by);
+    pack_tile(lds, job.src, job.dst, __builtin_amdgcn_readfirstlane(job.Cout), __builtin_amdgcn_readfirstlane(job.Cin),
+              __builtin_amdgcn_readfirstlane(job.T), __builtin_amdgcn_readfirstlane(job.ntaps), job.taps,
+              __builtin_amdgcn_readfirstlane(job.mode), job.dst_rows, job.dst_cols, job.row_off, job.col_off, bxi, byi, z);
 }
 
 extern "C" int t2v_pack_job_bytes(void) { return (int)sizeof(PackJob); }
 
-// `table`: DEVICE array of njobs PackJob records (layout: t2v_pack_job in the header); total_blocks = sum of bx*by*ntaps
+// `table`: DEVICE array of njobs PackJob records (layout: t2v_pack_job in the header); total_blocks = sum of
+// bx * by * t2v_pack_job_groups(T, ntaps, mode)
 extern "C" int t2v_pack_multi(const void* table, int njobs, int total_blocks, void* stream) {
     if (!table || njobs < 1 || total_blocks < 1) return T2V_EINVAL;
     T2V_LAUNCH(pack_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, (const PackJob*)table, njobs);
@@ -2132,28 +2208,18 @@ __global__ __launch_bounds__(256) void conv_igemm_bf16_strip3_kernel(const Group
 }
 
 // w[Cout][Cin][T] fp32 -> bf16 wpb[j][rows][K] with K contiguous: mode 0 rows = co, K = ci (forward);
-// mode 1 rows = ci, K = co, mirrored taps (data gradient)
-__global__ void pack_weight_bf16_kernel(const float* __restrict__ w, __bf16* __restrict__ wpb, int Cout, int Cin, int T,
-                                        TapList taps, int mode) {
-    const int j = blockIdx.y;
-    const int t = mode ? (T - 1 - taps.t[j]) : taps.t[j];
-    const long n = (long)Cout * Cin;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        int row, k;
-        if (mode == 0) { row = (int)(i / Cin); k = (int)(i - (long)row * Cin); wpb[(size_t)j * n + i] = (__bf16)w[((size_t)row * Cin + k) * T + t]; }
-        else { row = (int)(i / Cout); k = (int)(i - (long)row * Cout); wpb[(size_t)j * n + i] = (__bf16)w[((size_t)k * Cin + row) * T + t]; }
-    }
-}
+// mode 1 rows = ci, K = co, mirrored taps (data gradient). Same kernel and tile body as the fp32 packs (pack_tile modes 2 / 3).
 extern "C" int t2v_pack_weight_bf16(const float* w, void* wpb, int Cout, int Cin, int T, const int32_t* taps, int ntaps, int mode,
                                     void* stream) {
     if (!w || !wpb || !taps || Cout < 1 || Cin < 1 || T < 1 || ntaps < 1 || ntaps > T2V_MAX_TAPS) return T2V_EINVAL;
+    mode = mode ? 1 : 0;
     TapList tl;
     tl.n = ntaps;
     for (int i = 0; i < T2V_MAX_TAPS; ++i) tl.t[i] = i < ntaps ? taps[i] : 0;
-    long nb = ((long)Cout * Cin + 255) / 256;
-    if (nb > 1024) nb = 1024;
-    T2V_LAUNCH(pack_weight_bf16_kernel, dim3((unsigned)nb, (unsigned)ntaps), dim3(256), 0, (hipStream_t)stream, w, (__bf16*)wpb, Cout, Cin,
-               T, tl, mode);
+    const long nb = (long)((Cin + 31) / 32) * ((Cout + 31) / 32) * pack_job_groups(T, ntaps, 2 + mode);
+    if (nb > 0x7fffffffL) return T2V_EINVAL;
+    T2V_LAUNCH(pack_weight_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, wpb, Cout, Cin, T, tl, 2 + mode,
+               mode ? Cin : Cout, mode ? Cout : Cin, 0, 0);
     return launch_status();
 }
 

@@ -491,6 +491,14 @@ def _pack_job_of(p, key, hit):
     return (p, hit[2], Cout, Cin, geom.T, list(geom.taps), mode, (Cout if mode else Cin), (Cin if mode else Cout), 0, 0)
 
 
+def pack_job_groups(T, ntaps, mode):
+    """Third factor of a pack job's workgroup count (bx * by * this): stated by the library, see `t2v_pack_job_groups`."""
+    n = lib().t2v_pack_job_groups(T, ntaps, mode)
+    if n < 1:
+        raise ValueError('t2v_pack_job_groups(%d, %d, %d) = %d' % (T, ntaps, mode, n))
+    return n
+
+
 def repack_params(params):
     """Refresh every packed variant of these parameters in place, in ONE launch (`t2v_pack_multi`) driven by a
     device-resident job table that is rebuilt only when the set of cached variants changes. Called by the
@@ -522,7 +530,7 @@ def repack_params(params):
             a.block_begin = blocks
             for j, t in enumerate(taps):
                 a.taps[j] = t
-            blocks += a.bx * a.by * len(taps)
+            blocks += a.bx * a.by * pack_job_groups(T, len(taps), mode)
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone()
         dev = host.to(params[0].device)
         tab = (sig, dev, len(jobs), blocks)
