@@ -14,6 +14,7 @@
 #ifndef T2V_HIP_H
 #define T2V_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -861,6 +862,21 @@ int t2v_mbstd_fwd(const t2v_mbstd_member* members, int n, const float* w, int H,
 int t2v_mbstd_feat(const t2v_mbstd_member* members, int n, const float* w, int H, int K, int G, void* stream);
 int t2v_mbstd_second(const t2v_mbstd_member* members, int n, const float* w, int H, int K, int G, void* stream);
 int t2v_mbstd_weight(const t2v_mbstd_member* members, int n, float* W, int H, int K, int G, int accum, void* stream);
+
+/* ---- Gram sums of the Kernel Inception Distance estimator (Binkowski et al. 2018; opt-in evaluation, --eval_period) ----
+ * One definition. X (real) and Y (generated) are dense fp32 [n, d] feature matrices; with a block size s (n % s == 0, nb = n / s)
+ * rows [b*s, (b+1)*s) of X and of Y form block b, and with k(u, v) = (alpha u.v + 1)^3
+ *   out[b][0] = sum_{i != j in block b} k(x_i, x_j)
+ *   out[b][1] = sum_{i != j in block b} k(y_i, y_j)
+ *   out[b][2] = sum_{i, j in block b} k(x_i, y_j)                                                    (diagonal included)
+ * out is dense double [nb][3]; nothing crosses a block boundary; s = n is the full estimator. fp64 throughout: the features are
+ * widened on load, the dot products run on v_mfma_f64_16x16x4_f64, the cube and all sums are double. d and s need not be
+ * multiples of anything. Two launches (per-tile partials into ws, then their sum in one fixed order), no atomics: the same bits
+ * run to run. X and Y are only read; out and ws must not alias them. ws holds t2v_kid_sums_ws_bytes(n, d, s) bytes (0 for sizes
+ * the entry point refuses), 8-byte aligned. Neither allocates or synchronises.
+ * T2V_EINVAL, before any launch, on X, Y, out or ws == NULL, n < 2, d < 1, s < 2, s > n, n % s != 0, n / s > 65535 or a NaN alpha. */
+int t2v_kid_sums(const float* X, const float* Y, int n, int d, int s, double alpha, double* out, void* ws, void* stream);
+size_t t2v_kid_sums_ws_bytes(int n, int d, int s);
 
 #ifdef __cplusplus
 }

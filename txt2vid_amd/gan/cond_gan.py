@@ -40,6 +40,7 @@ class CondGan(object):
         self.discrim_sn = None            # gan.spectral.SpectralNorm of `discrims` (--D_sn, not in the reference), or None
         self.ada = None                   # gan.ada.AdaState, the controller of the augmentation's p (--D_ada, not in the reference), or None
         self.lecam = None                 # gan.lecam.LeCamState, the anchors of the LeCam term (--D_lecam, not in the reference), or None
+        self.kid = None                   # gan.kid.KidEvaluator (--eval_period, not in the reference), or None: in no checkpoint
 
     def _observe(self, discrim, u_r, u_f):
         """--D_ada: the unconditional logits of the `lu` term of a D step feed the controller (the first discriminator's alone):

@@ -1,7 +1,8 @@
 """Training loop of the TGANv2 hot path — same entry points and flags as txt2vid/gan/trainer.py
 (`add_params_to_parser`, `train`, `test`), with the loop body factored into `train_iteration` so that
 bench.py and the parity tests drive exactly what `train()` runs. `train()` meets the opt-in features that log or are read with the
-losses (ada, lr schedule, gradient guard) through gan/extras.py and names none of them.
+losses (ada, lr schedule, gradient guard) through gan/extras.py and names none of them; the KID evaluation (`gan.kid`) is
+two calls outside the step: `observe` in front of it until the real bank is full, `step` next to the sample-writing block.
 
 Random draws follow the reference order on the HOST generators (SURVEY §7 "RNG parity"): 4x Subsample
 phase (trainer.py:157-158), z (trainer.py:221, drawn on the CPU and copied), 3x Subsample in G,
@@ -68,7 +69,8 @@ def _positive(kind, flag):
 def add_params_to_parser(parser):
     """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema,
     --G_ema_start, --D_aug, --D_aug_p, --D_ada, --D_ada_interval, --D_ada_kclips, --D_lecam, --D_lecam_decay, --D_lecam_start,
-    --D_sn, --lr_decay, --lr_decay_iters, --lr_decay_start, --lr_final, --grad_guard, --D_clip and --G_clip are new."""
+    --D_sn, --lr_decay, --lr_decay_iters, --lr_decay_start, --lr_final, --grad_guard, --D_clip, --G_clip, --eval_period,
+    --eval_clips, --eval_block and --eval_net are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
     parser.add_argument('--log_period', type=int, default=20)
@@ -141,6 +143,8 @@ def add_params_to_parser(parser):
                              '(torch.nn.utils.clip_grad_norm_ semantics); implies --grad_guard')
     parser.add_argument('--G_clip', type=float, default=None, metavar='C',
                         help="(new) clip the generator's gradients to global L2 norm C > 0; implies --grad_guard")
+    from .kid import add_flags as add_kid_flags
+    add_kid_flags(parser)                  # --eval_period, --eval_clips, --eval_block, --eval_net (new)
     return parser
 
 
@@ -698,6 +702,7 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
     from ..data import DevicePrefetcher
     from ..dist import rank_world
     writer = rank_world()[0] == 0            # data-parallel replicas are identical: rank 0 alone writes checkpoints and samples
+    kid = getattr(gan, 'kid', None) if writer else None      # --eval_period: the writer alone, from its local batches
     iteration = 0
     # HIP-graph replay of the iteration (see GraphedTrainStep) unless --no_graph / --end2end: the eager loop is
     # host-bound (~1 000 launches at ~20 us of Python each)
@@ -729,6 +734,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                     _, _, cond = gan.cond_encoder.encode(y[0], y[1])
                     if not end2end:
                         cond = cond.detach()
+            if kid is not None and not kid.full:
+                kid.observe(x, cond)             # the first clips of the run fill the real bank (eager launches, between replays)
             if use_graph:
                 key = (tuple(x.shape), None if cond is None else tuple(cond.shape))
                 if graphed is None or key != graphed_key:          # first batch (or a new batch shape): capture again
@@ -794,6 +801,8 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
                 if cond is not None and vocab is not None:
                     save_sentences(y[0], path='%s/sentences_epoch%03d_iter_%06d.txt' % (params.out_samples, epoch, iteration),
                                    vocab=vocab)
+            if kid is not None:
+                kid.step(iteration)              # evaluates, logs and appends to <out>/metrics.jsonl when one is due
             load_watch.start()
             iter_watch.stop()
             avg_iter.update(iter_watch.elapsed_time)

@@ -34,8 +34,32 @@ def _model(spec, args, kind='D', **kw):
     return create_object(spec, **kw)
 
 
-def main(args):
-    from ..gan import ada, grad_guard, lecam, lr_sched
+def _dataset(args, vocab, rank):
+    transform = data.default_transform(frame_size=[args.frame_sizes[-1]], num_channels=args.num_channels)
+    return create_object(args.data, vocab=vocab, anno=args.anno, transform=transform, size=args.frame_sizes[-1],
+                         channels=args.num_channels, seed=(args.seed or 0) + rank)
+
+
+def _epoch_clips(args, world):
+    """Clips the writer rank sees in one epoch (whole batches), from a dataset object built for the count alone; the host
+    generators are left as they were."""
+    import random
+    import numpy as np
+    state = (random.getstate(), np.random.get_state())
+    try:
+        with torch.random.fork_rng(devices=[]):
+            dset = _dataset(args, load(args.vocab) if args.vocab else data.Vocab(), 0)
+    finally:
+        random.setstate(state[0])
+        np.random.set_state(state[1])
+    per_rank = len(dset) if isinstance(dset, data.SyntheticMovingDigits) else len(dset) // world
+    return per_rank // args.batch_size * args.batch_size
+
+
+def construct(args):
+    """Everything `main` builds in front of the loop, as a dict (gan, optD, optG, losses, dataset, device, vocab, grad_sync, ck):
+    the stand-alone evaluation (gan/kid.py) builds its models through here too."""
+    from ..gan import ada, grad_guard, kid, lecam, lr_sched
     from ..gan.ema import GenAverage
     from ..gan.spectral import check_flags, check_checkpoint, SpectralNorm, attach
     # the flags' rules are checked before a process group forms (a data-parallel start with --D_ada is refused here)
@@ -44,6 +68,8 @@ def main(args):
     lecam.check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
     lr_sched.check_args(args)
     grad_guard.check_args(args)
+    kid.check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')),
+                   epoch_clips=lambda: _epoch_clips(args, int(os.environ.get('WORLD_SIZE', '1'))))
     from .. import dist as tdist
     rank, world = tdist.init_from_env('nccl')
     from ..util.misc import limit_host_threads
@@ -177,12 +203,14 @@ def main(args):
         status('Spectral normalisation of %d discriminator weights (%s)' % (
             len(gan.discrim_sn.params), 'state from the checkpoint' if 'discrim_sn' in ck else '%d initial power iterations'
             % gan.discrim_sn.n_init))
+    if getattr(args, 'eval_period', 0) > 0 and rank == 0:
+        # (the writer alone. Its feature network is initialised under a seed of its own with the host generators
+        # forked, its latents come from a device generator of its own: no draw of the training loop moves)
+        gan.kid = kid.from_args(gan, args, device)
     if ck.get('rng_state') is not None and rank == 0:
         # the writer's (rank 0's) generator states: the run continues the saved draw sequence (reference files have no such key)
         set_rng_state(ck['rng_state'])
-    transform = data.default_transform(frame_size=[args.frame_sizes[-1]], num_channels=args.num_channels)
-    dset = create_object(args.data, vocab=vocab, anno=args.anno, transform=transform, size=args.frame_sizes[-1],
-                         channels=args.num_channels, seed=(args.seed or 0) + rank)
+    dset = _dataset(args, vocab, rank)
     dataset = data.get_loader(dset=dset, batch_size=args.batch_size, val=False, num_workers=args.workers, rank=rank,
                               world=world, seed=seed, device=device)
     status('GAN has %d parameters' % gan.count_params())
@@ -196,6 +224,14 @@ def main(args):
         shared = [txt_encoder] if (args.end2end and txt_encoder is not None) else []
         arenas = {'D': tdist.model_arena(list(discrims) + shared, TF.copy_into), 'G': tdist.model_arena([gen] + shared, TF.copy_into)}
         grad_sync = tdist.make_grad_sync(arenas, {'D': optD, 'G': optG}, world)
+    return {'gan': gan, 'optD': optD, 'optG': optG, 'losses': losses, 'dataset': dataset, 'device': device, 'vocab': vocab,
+            'grad_sync': grad_sync, 'ck': ck}
+
+
+def main(args):
+    c = construct(args)
+    gan, optD, optG, losses, dataset, device, vocab, grad_sync = (c[k] for k in ('gan', 'optD', 'optG', 'losses', 'dataset', 'device',
+                                                                                 'vocab', 'grad_sync'))
     if args.test:
         test(gan=gan, num_samples=args.num_samples, dataset=dataset, device=device, params=args,
              channel_first=not args.sequence_first, vocab=vocab)
