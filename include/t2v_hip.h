@@ -878,6 +878,32 @@ int t2v_mbstd_weight(const t2v_mbstd_member* members, int n, float* W, int H, in
 int t2v_kid_sums(const float* X, const float* Y, int n, int d, int s, double alpha, double* out, void* ws, void* stream);
 size_t t2v_kid_sums_ws_bytes(int n, int d, int s);
 
+/* ---- k-nearest-neighbour radii and counts of precision/recall (Kynkaanniemi et al. 2019) and density/coverage (Naeem et al. 2020) ----
+ * (opt-in evaluation, --eval_prdc)
+ * One definition. X (real) and Y (generated) are dense fp32 [n, d] feature matrices, k an integer with 1 <= k <= T2V_KNN_MAX_K and
+ * k < n. D2(u, v) = max(0, |u|^2 + |v|^2 - 2 u.v). rX[i] is the k-th smallest of D2(x_i, x_l) over l != i — a SQUARED radius, self
+ * excluded by index, not by value — and rY[j] the same within Y. The counts, all integers:
+ *   c[0] = #{ j : exists i, D2(x_i, y_j) <= rX[i] }                                                  (precision * n)
+ *   c[1] = sum_j #{ i : D2(x_i, y_j) <= rX[i] }                                                      (density * k * n)
+ *   c[2] = #{ i : exists j, D2(x_i, y_j) <= rY[j] }                                                  (recall * n)
+ *   c[3] = #{ i : min_j D2(x_i, y_j) <= rX[i] }                                                      (coverage * n)
+ * The four divisions are the host's. The whole bank takes part: there are no blocks.
+ * t2v_knn_radii writes the radii of one bank U as double [n]; t2v_prdc_counts reads both banks and both radii and writes
+ * int64 [4]. fp64 throughout: the features are widened on load, the dot products run on v_mfma_f64_16x16x4_f64, the row norms are
+ * double. No n x n matrix reaches memory: the selection happens on each 64x64 tile, per-tile partials go into ws and a second
+ * launch folds them (three launches each, the first the row norms). The same bits run to run: the k smallest of a multiset and an
+ * integer sum have no order. n and d need not be multiples of anything. U, X, Y, rX, rY are only read; the outputs and ws must
+ * not alias them. ws holds t2v_knn_radii_ws_bytes(n, d, k) or t2v_prdc_counts_ws_bytes(n, d, k) bytes (0 for sizes the entry point
+ * refuses; O(n * ceil(n / 64) * k) and O(n * ceil(n / 64))), 8-byte aligned; it need not be initialised. Neither allocates or
+ * synchronises.
+ * T2V_EINVAL, before any launch, on a NULL pointer, n < 2, d < 1, k < 1, k > T2V_KNN_MAX_K, k >= n or ceil(n / 64) > 65535. */
+#define T2V_KNN_MAX_K 16
+int t2v_knn_radii(const float* U, int n, int d, int k, double* r2_out, void* ws, void* stream);
+size_t t2v_knn_radii_ws_bytes(int n, int d, int k);
+int t2v_prdc_counts(const float* X, const float* Y, int n, int d, int k, const double* rX, const double* rY, int64_t* counts_out,
+                    void* ws, void* stream);
+size_t t2v_prdc_counts_ws_bytes(int n, int d, int k);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,14 +8,19 @@ generated clips, in blocks of S clips (functional_kid.py; fp64 on the matrix pip
 a seed that is a constant of this file, so numbers compare across runs — or, with `--eval_net PATH`, the discriminator trunk of a
 checkpoint. Numbers compare only under the same feature network.
 
+`--eval_prdc K` adds improved precision/recall (Kynkäänniemi et al. 2019) and density/coverage (Naeem et al. 2020) on
+the same two banks with K nearest neighbours (functional_prdc.py; the whole bank, no blocks): fidelity and diversity apart, where
+KID is one number. They compare only under the same feature network, K and M.
+
 Isolation: the evaluator owns its network (frozen, eval mode, in no optimiser and no checkpoint), its latents and its draws (a
 device generator and a draws object of its own), restores the generator's mode and weights, and reads the host generators'
 state back, so a run with the flag computes bit for bit what it computes without it.
 
     python -m txt2vid_amd.gan.kid --weights CKPT --data SPEC [the model flags of train.gan]
 
-evaluates a finished run: the models are built as `train.gan` builds them, the real bank is filled from the loader, one JSON line
-is printed."""
+evaluates a finished run: the models are built as `train.gan` builds them, the real bank is filled from the loader — under the
+run's --seed and flags with the clips the run's first iterations saw — and one JSON line is printed (with `--eval_prdc K`, the
+extended record)."""
 import contextlib
 import json
 import math
@@ -26,6 +31,7 @@ import torch
 from .. import functional as TF
 from ..draws import HostDraws
 from ..functional_kid import kid_sums_raw, estimate
+from .. import functional_prdc as FP
 from ..util.log import status
 
 FEATURE_SEED = 20181                  # the random feature network's seed: a constant of the code, never the run's --seed
@@ -46,6 +52,9 @@ def add_flags(parser):
     parser.add_argument('--eval_net', type=str, default=None, metavar='PATH',
                         help="(new) take the feature network of --eval_period from this checkpoint's discriminator trunk instead "
                              'of the fixed random initialisation')
+    parser.add_argument('--eval_prdc', type=int, default=0, metavar='K',
+                        help='(new) with --eval_period, also precision/recall and density/coverage of the same features with K '
+                             'nearest neighbours, 1..16 (5: Naeem et al. 2020; 3: Kynkäänniemi et al. 2019); 0 = off')
     return parser
 
 
@@ -55,6 +64,11 @@ def check_args(args, world=1, epoch_clips=None):
     period = getattr(args, 'eval_period', 0) or 0
     if period < 0:
         raise ValueError('--eval_period takes a number of iterations >= 0 (0 = off), got %d' % period)
+    K = getattr(args, 'eval_prdc', 0) or 0
+    if K < 0 or K > FP.MAX_K:
+        raise ValueError('--eval_prdc takes a number of neighbours from 1 to %d (0 = off), got %d' % (FP.MAX_K, K))
+    if K > 0 and period == 0:
+        raise ValueError('--eval_prdc %d needs --eval_period: the metrics are computed on the banks of that evaluation' % K)
     if period == 0:
         return
     M = args.eval_clips
@@ -68,6 +82,8 @@ def check_args(args, world=1, epoch_clips=None):
                          'encoder that has moved on since')
     if args.eval_net is not None and not os.path.exists(args.eval_net):
         raise ValueError('--eval_net %s: no such file' % args.eval_net)
+    if K >= M:
+        raise ValueError('--eval_prdc %d needs more than %d clips (--eval_clips): a clip has M - 1 neighbours' % (K, M))
     args.eval_block = S
     if epoch_clips is not None:
         have = int(epoch_clips())
@@ -142,7 +158,7 @@ class KidEvaluator(object):
     M clips from fixed latents and returns the record; `due(iteration)` says when."""
 
     def __init__(self, gan, device, clips=2048, block=None, num_channels=1, seed=LATENT_SEED, period=1, sample_batch=None,
-                 net=None, out_dir=None):
+                 net=None, out_dir=None, prdc=0):
         block = min(clips, 1024) if block is None else block
         if clips < 2 or block < 2 or clips % block:
             raise ValueError('KID takes M >= 2 clips in whole blocks of S >= 2, got M = %d, S = %d' % (clips, block))
@@ -163,6 +179,17 @@ class KidEvaluator(object):
         self.sums = torch.zeros(self.M // self.S, 3, device=device, dtype=torch.float64)
         need = int(TF.lib().t2v_kid_sums_ws_bytes(self.M, self.dim, self.S))
         self.ws = torch.zeros(need // 8 + 1, device=device, dtype=torch.float64).view(torch.uint8)
+        self.prdc = int(prdc or 0)                              # --eval_prdc K: neighbours of precision/recall/density/coverage, 0 = off
+        if self.prdc:
+            FP.check_sizes(self.M, self.dim, self.prdc)
+            L = TF.lib()
+            need = max(int(L.t2v_knn_radii_ws_bytes(self.M, self.dim, self.prdc)), int(L.t2v_prdc_counts_ws_bytes(self.M, self.dim, self.prdc)))
+            if need < 1:
+                raise ValueError('PRDC: no launch plan for M = %d, k = %d' % (self.M, self.prdc))
+            self.prdc_ws = torch.zeros(need // 8 + 1, device=device, dtype=torch.float64).view(torch.uint8)
+            self.rX = torch.zeros(self.M, device=device, dtype=torch.float64)       # squared radii of the real bank: once, when it fills
+            self.rY = torch.zeros(self.M, device=device, dtype=torch.float64)
+            self.counts = torch.zeros(4, device=device, dtype=torch.int64)
         self.last = None
         self._waiting_logged = False
 
@@ -197,6 +224,8 @@ class KidEvaluator(object):
             if not mean > 0 or not math.isfinite(mean):
                 raise RuntimeError('KID: the real features have mean squared norm %r' % mean)
             self.alpha = 1.0 / mean
+            if self.prdc:
+                FP.knn_radii_raw(self.real_bank, self.prdc, out=self.rX, ws=self.prdc_ws)
 
     def due(self, iteration):
         return self.period > 0 and iteration % self.period == 0
@@ -234,15 +263,25 @@ class KidEvaluator(object):
             raise RuntimeError('KID: the real bank holds %d of %d clips' % (self.filled, self.M))
         self._render()
         kid_sums_raw(self.real_bank, self.fake_bank, self.S, self.alpha, out=self.sums, ws=self.ws)
+        if self.prdc:
+            FP.knn_radii_raw(self.fake_bank, self.prdc, out=self.rY, ws=self.prdc_ws)
+            FP.prdc_counts_raw(self.real_bank, self.fake_bank, self.prdc, self.rX, self.rY, out=self.counts, ws=self.prdc_ws)
         kid, stderr, _ = estimate(self.sums.tolist(), self.S)
         self.last = {'iteration': int(iteration), 'kid': kid, 'stderr': stderr, 'clips': self.M, 'block': self.S,
                      'alpha': self.alpha, 'net': self.net_name}
+        if self.prdc:
+            p, r, d, c = FP.estimate(self.counts.tolist(), self.M, self.prdc)
+            self.last.update({'precision': p, 'recall': r, 'density': d, 'coverage': c, 'prdc_k': self.prdc})
         return self.last
 
     def log_line(self, rec):
         pm = '' if rec['stderr'] is None else ' ± %.5f' % rec['stderr']
         return 'Iter %d, KID: %.5f%s (%d clips in blocks of %d; features: %s)' % (rec['iteration'], rec['kid'], pm, rec['clips'],
                                                                                    rec['block'], rec['net'])
+
+    def prdc_line(self, rec):
+        return 'Iter %d, PRDC (k=%d): precision %.3f, recall %.3f, density %.3f, coverage %.3f' % (
+            rec['iteration'], rec['prdc_k'], rec['precision'], rec['recall'], rec['density'], rec['coverage'])
 
     def step(self, iteration):
         """What train() calls behind an iteration: evaluate, log and append to <out>/metrics.jsonl when one is due."""
@@ -255,6 +294,8 @@ class KidEvaluator(object):
             return None
         rec = self.evaluate(iteration)
         status(self.log_line(rec))
+        if self.prdc:
+            status(self.prdc_line(rec))
         if self.out_dir is not None:
             with open(os.path.join(self.out_dir, METRICS_FILE), 'a') as f:
                 f.write(json.dumps(rec) + '\n')
@@ -265,9 +306,12 @@ def from_args(gan, args, device):
     """The evaluator of a run (main(): behind sync_replicas, in front of set_rng_state), announced in the log."""
     ev = KidEvaluator(gan, device, clips=args.eval_clips, block=args.eval_block, num_channels=args.num_channels,
                       period=args.eval_period, sample_batch=args.sample_batch_size or args.batch_size, net=args.eval_net,
-                      out_dir=args.out)
+                      out_dir=args.out, prdc=getattr(args, 'eval_prdc', 0))
     status('KID evaluation every %d iterations: %d clips in blocks of %d; features: %s. Numbers compare only under the same '
            'feature network' % (ev.period, ev.M, ev.S, ev.net_name))
+    if ev.prdc:
+        status('with precision/recall and density/coverage on the same features, k = %d nearest neighbours among all %d clips'
+               % (ev.prdc, ev.M))
     return ev
 
 
@@ -279,7 +323,9 @@ def main(argv=None):
     if args.weights is None:
         raise SystemExit('txt2vid_amd.gan.kid evaluates a checkpoint: pass --weights')
     args.eval_period = args.eval_period or 1
-    built = train_gan.construct(args)
+    # the real bank of a run is its first M clips: the loader has to start where the run's did, not where the checkpoint's draw
+    # sequence goes on. Under the run's --seed and flags the record of a checkpoint is then the one the run logged at that iteration
+    built = train_gan.construct(args, continue_draws=False)
     gan, device, ev = built['gan'], built['device'], built['gan'].kid
     pre = DevicePrefetcher(built['dataset'], device)
     x, y = pre.next()
@@ -293,6 +339,8 @@ def main(argv=None):
         x, y = pre.next()
     rec = ev.evaluate(int(built['ck'].get('iteration', 0)))
     status(ev.log_line(rec))
+    if ev.prdc:
+        status(ev.prdc_line(rec))
     print(json.dumps(rec), flush=True)
     return rec
 

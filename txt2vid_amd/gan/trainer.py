@@ -70,7 +70,7 @@ def add_params_to_parser(parser):
     """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema,
     --G_ema_start, --D_aug, --D_aug_p, --D_ada, --D_ada_interval, --D_ada_kclips, --D_lecam, --D_lecam_decay, --D_lecam_start,
     --D_sn, --lr_decay, --lr_decay_iters, --lr_decay_start, --lr_final, --grad_guard, --D_clip, --G_clip, --eval_period,
-    --eval_clips, --eval_block and --eval_net are new."""
+    --eval_clips, --eval_block, --eval_net and --eval_prdc are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
     parser.add_argument('--log_period', type=int, default=20)
@@ -144,7 +144,7 @@ def add_params_to_parser(parser):
     parser.add_argument('--G_clip', type=float, default=None, metavar='C',
                         help="(new) clip the generator's gradients to global L2 norm C > 0; implies --grad_guard")
     from .kid import add_flags as add_kid_flags
-    add_kid_flags(parser)                  # --eval_period, --eval_clips, --eval_block, --eval_net (new)
+    add_kid_flags(parser)                  # --eval_period, --eval_clips, --eval_block, --eval_net, --eval_prdc (new)
     return parser
 
 

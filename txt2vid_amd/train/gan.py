@@ -56,9 +56,11 @@ def _epoch_clips(args, world):
     return per_rank // args.batch_size * args.batch_size
 
 
-def construct(args):
+def construct(args, continue_draws=True):
     """Everything `main` builds in front of the loop, as a dict (gan, optD, optG, losses, dataset, device, vocab, grad_sync, ck):
-    the stand-alone evaluation (gan/kid.py) builds its models through here too."""
+    the stand-alone evaluation (gan/kid.py) builds its models through here too — with `continue_draws=False`, which leaves the
+    host generators where a fresh run under --seed has them instead of continuing the checkpoint's draw sequence, so that its
+    loader yields the clips the run's first iterations saw."""
     from ..gan import ada, grad_guard, kid, lecam, lr_sched
     from ..gan.ema import GenAverage
     from ..gan.spectral import check_flags, check_checkpoint, SpectralNorm, attach
@@ -207,7 +209,7 @@ def construct(args):
         # (the writer alone. Its feature network is initialised under a seed of its own with the host generators
         # forked, its latents come from a device generator of its own: no draw of the training loop moves)
         gan.kid = kid.from_args(gan, args, device)
-    if ck.get('rng_state') is not None and rank == 0:
+    if ck.get('rng_state') is not None and rank == 0 and continue_draws:
         # the writer's (rank 0's) generator states: the run continues the saved draw sequence (reference files have no such key)
         set_rng_state(ck['rng_state'])
     dset = _dataset(args, vocab, rank)
