@@ -185,7 +185,7 @@ def test_deferred_weight_gradient_reduce(cin, cout, k, members):
         with torch.no_grad():
             # one source: bit-identical to the immediate path
             TF.grad_sink_reset()
-            done, gw = TF._to_sink_w(w, sets[0][0], sets[0][1], True)
+            done, gw, _ = TF._conv_wgrad_to_sink(w, None, sets[0][0], sets[0][1], True)
             assert done and gw is not None and sink.pending
             TF.grad_sink_flush()
             assert not sink.pending
@@ -193,7 +193,7 @@ def test_deferred_weight_gradient_reduce(cin, cout, k, members):
             # three sources of the same weight (+ bias through the fused side sums when Cin >= 64)
             TF.grad_sink_reset()
             for r, (xs, gys) in enumerate(sets):
-                done, gw_r, gb_r = TF._to_sink_wb(w, b, xs, gys, True)
+                done, gw_r, gb_r = TF._conv_wgrad_to_sink(w, b, xs, gys, True)
                 assert done and (gw_r is None) == (r > 0)
             TF.grad_sink_flush()
             views = arena.views()
@@ -201,11 +201,11 @@ def test_deferred_weight_gradient_reduce(cin, cout, k, members):
             close(views[1], db_ref, rtol=1e-5, atol=1e-5)
             # an immediate producer of the same parameter while a slab is pending: the pending part lands first
             TF.grad_sink_reset()
-            TF._to_sink_w(w, sets[0][0], sets[0][1], True)
+            TF._conv_wgrad_to_sink(w, None, sets[0][0], sets[0][1], True)
             extra = rnd(99, *w.shape).to(dev())
             done, _ = TF._to_sink(w, lambda out, acc: TF.copy_into(out + extra, out) if acc else TF.copy_into(extra, out))
             assert done and not sink.pending
-            TF._to_sink_w(w, sets[1][0], sets[1][1], True)
+            TF._conv_wgrad_to_sink(w, None, sets[1][0], sets[1][1], True)
             TF.grad_sink_flush()
             want = dw1 + extra + TF.conv_group_wgrad_raw(sets[1][0], sets[1][1], tuple(w.shape), True)
             close(arena.views()[0], want, rtol=1e-5, atol=1e-5)

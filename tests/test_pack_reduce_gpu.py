@@ -129,6 +129,77 @@ def test_repack_params_three_kernel_extents_in_one_table():
     assert len({p[2] for p in packed}) == 3
 
 
+def test_fused_gate_packs_persist_across_repack(monkeypatch):
+    """The ConvLSTM's fused gate matrices (`packed_fused`: four [8,8,3,3] parameters seen as [8,8,1,3,3] views, two stored tap-major
+    and two dense; modes 0 / 1; the 9 taps and the single live tap of a 1x1 map) next to the plain fp32 / bf16 packs of one of the
+    same parameters. After an in-place update + `bump_weight_epoch` + `repack_params` every buffer sits at the same address and
+    equals, bit for bit, a fresh pack through the single-tensor entry points; a second lookup, through new `unsqueeze(2)` views,
+    returns the same buffers without calling a pack entry point."""
+    TF, L = _env()[:2]
+    from txt2vid_amd import _lib
+    Cc, n = 8, 4
+    torch.manual_seed(11)
+    params = [torch.nn.Parameter(TF.tap_major(torch.randn(Cc, Cc, 3, 3).to(DEV)) if i < 2 else torch.randn(Cc, Cc, 3, 3).to(DEV))
+              for i in range(n)]
+    assert [TF.is_tap_major(p) for p in params] == [True, True, False, False]
+    tapsets = []
+    for hw in (4, 1):
+        g = TF.conv_geom(2, Cc, 1, hw, hw, n * Cc, 1, 3, 3)
+        tapsets.append(TF._tapset(g.T, g.mask))
+    assert [len(ts.taps) for ts in tapsets] == [9, 1]
+    dense = params[2]
+
+    def lookups():
+        """[(buffer, fresh pack into a scratch buffer)] of every variant, through views made for this call."""
+        out = []
+        for ts in tapsets:
+            for mode in (0, 1):
+                def fresh_fused(dst, ts=ts, mode=mode):
+                    rows, cols = (Cc, n * Cc) if mode == 0 else (n * Cc, Cc)
+                    for i, p in enumerate(params):
+                        ro, co = (0, i * Cc) if mode == 0 else (i * Cc, 0)
+                        TF.check(L.t2v_pack_weight_into(TF._p(p), TF._p(dst), Cc, Cc, ts.T, ts.taps_c, len(ts.taps), mode | (8 if i < 2 else 0),
+                                                        rows, cols, ro, co, TF._stream()), 'into')
+                out.append((TF.packed_fused([p.unsqueeze(2) for p in params], ts, mode), fresh_fused))
+        ts = tapsets[0]
+        for mode in (0, 1):
+            out.append((TF.packed_weight(dense.unsqueeze(2), ts, mode), lambda dst, mode=mode: TF.check(L.t2v_pack_weight(
+                TF._p(dense), TF._p(dst), Cc, Cc, ts.T, ts.taps_c, len(ts.taps), mode, TF._stream()), 'pack')))
+            out.append((TF.packed_weight_bf16(dense.unsqueeze(2), ts, mode), lambda dst, mode=mode: TF.check(L.t2v_pack_weight_bf16(
+                TF._p(dense), TF._p(dst), Cc, Cc, ts.T, ts.taps_c, len(ts.taps), mode, TF._stream()), 'pack16')))
+        return out
+    first = lookups()
+    assert len({wp.data_ptr() for wp, _ in first}) == len(first) == 8
+    ptrs = [wp.data_ptr() for wp, _ in first]
+    with torch.no_grad():
+        for p in params:
+            p.copy_(torch.randn(Cc, Cc, 3, 3).to(DEV))           # (keeps each parameter's memory layout)
+    assert [TF.is_tap_major(p) for p in params] == [True, True, False, False]
+    TF.bump_weight_epoch(params)
+    TF.repack_params(params)
+    torch.cuda.synchronize()
+    for (wp, fresh), ptr in zip(first, ptrs):
+        assert wp.data_ptr() == ptr
+        ref = torch.full_like(wp, SENTINEL)
+        fresh(ref)
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(wp), _bits(ref)), (tuple(wp.shape), wp.dtype)
+    calls = []
+
+    def wrap(name, orig):
+        def f(*a):
+            calls.append(name)
+            return orig(*a)
+        return f
+    with monkeypatch.context() as mp:
+        for name in _lib.SIGNATURES:
+            mp.setattr(L, name, wrap(name, getattr(L, name)))
+        again = lookups()
+    torch.cuda.synchronize()
+    assert not {'t2v_pack_weight', 't2v_pack_weight_into', 't2v_pack_weight_bf16'} & set(calls), calls
+    assert [wp.data_ptr() for wp, _ in again] == ptrs
+
+
 # ---------------------------------------------------------------------------------------------- reduce
 def _reduce_dests(kind, values):
     """Destinations of one table for `kind`: T x CoCi x S, with 1-3 sources whose maps have -1 entries, a tap no source touches,

@@ -357,24 +357,24 @@ def _fresh_pack_matches(params):
     from txt2vid_amd import functional as TF
     n = 0
     for p in params:
-        for key, hit in TF._pack_cache.get(id(p), {}).items():
-            if hit[0]() is not p or key[0] == 'bf16':
+        for key, rec in TF._pack_cache.get(id(p), {}).items():
+            if rec.ref() is not p or rec.kind == 'bf16':
                 continue
-            if key[0] == 'fused':
-                w, wp, Cout, Cin, T, taps, mode, rows, cols, ro, co = hit[4]
+            w, Cout, Cin, T, taps, mode, rows, cols, ro, co = rec.job
+            taps_c = (C.c_int32 * len(taps))(*taps)
+            if rec.kind == 'fused':
+                wp = rec.buf
                 fresh = torch.zeros_like(wp)
-                taps_c = (C.c_int32 * len(taps))(*taps)
                 TF.check(TF.lib().t2v_pack_weight_into(TF._p(w), TF._p(fresh), Cout, Cin, T, taps_c, len(taps), mode, rows, cols, ro, co,
                                                        TF._stream()), 't2v_pack_weight_into')
                 mask = fresh != 0
                 assert bool(mask.any()) and torch.equal(fresh[mask], wp[mask]), key
             else:
                 shape5, _, mode = key
-                geom = hit[3]
-                fresh = torch.empty_like(hit[2])
-                TF.check(TF.lib().t2v_pack_weight(TF._p(p.detach().view(shape5)), TF._p(fresh), shape5[0], shape5[1], geom.T, geom.taps_c,
-                                                  len(geom.taps), mode, TF._stream()), 't2v_pack_weight')
-                assert torch.equal(fresh, hit[2]), key
+                fresh = torch.empty_like(rec.buf)
+                TF.check(TF.lib().t2v_pack_weight(TF._p(p.detach().view(shape5)), TF._p(fresh), shape5[0], shape5[1], T, taps_c,
+                                                  len(taps), mode, TF._stream()), 't2v_pack_weight')
+                assert torch.equal(fresh, rec.buf), key
             n += 1
     return n
 

@@ -106,10 +106,10 @@ def child(out_dir):
     seen = set()
     for tag, model in (('G', gen), ('D', dis)):
         for pname, p in model.named_parameters():
-            for key, hit in (TF._pack_cache.get(id(p)) or {}).items():
-                if hit[0]() is p and hit[2].data_ptr() not in seen:
-                    seen.add(hit[2].data_ptr())
-                    save('flagship-%s-%s-pack%02d' % (tag, pname, len([n for n in names if n.startswith('flagship-%s-%s-' % (tag, pname))])), hit[2])
+            for key, rec in (TF._pack_cache.get(id(p)) or {}).items():
+                if rec.ref() is p and rec.buf.data_ptr() not in seen:
+                    seen.add(rec.buf.data_ptr())
+                    save('flagship-%s-%s-pack%02d' % (tag, pname, len([n for n in names if n.startswith('flagship-%s-%s-' % (tag, pname))])), rec.buf)
     sink = gan.__dict__['_t2v_grad_sink'][1]
     for i, arena in enumerate({id(s[0]): s[0] for s in sink.slots.values()}.values()):
         save('flagship-grad-arena%d' % i, arena.flat)

@@ -192,7 +192,6 @@ class GradSink(object):
         _side.join()                                       # (slabs written on the side stream)
         arr = (WgradDest * len(dests))()
         blocks = 0
-        sig = []
         for a, d in zip(arr, dests):
             a.dw, a.dbias, a.CoCi, a.T, a.Cout = d.dw, d.dbias or None, d.CoCi, d.T, d.Cout
             a.nsrc, a.accum, a.accum_bias, a.tap_major = len(d.srcs), d.accum, d.accum_bias, d.tap_major
@@ -291,42 +290,37 @@ def grad_sink_flush():
         _grad_sink.flush()
 
 
-def _to_sink_wb(w, b, xs, gys, relu_in, even_frames=False):
-    """Weight AND bias gradient of one (grouped) convolution into their sink slots with ONE weight-gradient launch
-    (`t2v_conv_wgrad_grouped_bias`: the 3-tap-row kernel sums the dL/dy tiles it stages anyway). Returns
-    (handled, gw, gb) like `_to_sink`."""
-    if _grad_sink is None or w is None or b is None or torch.is_grad_enabled():
+def _wgrad_to_sink(w, b, launch_partial, launch_direct):
+    """Weight (and, with `b`, bias) gradient of one convolution into the sink slots of its parameters: the ONE place that
+    resolves the slots (weight first), chooses between the deferred and the immediate reduce and registers the slab.
+    `launch_partial(sink)` runs the weight-gradient main kernel alone and returns (WgradSrc, slab);
+    `launch_direct(dw, accum, dbias, accum_bias)` runs it with its reduce pass. Nothing goes to the sink while autograd records,
+    or unless every parameter asked for has a slot. Returns (handled, gw, gb) like `_to_sink`: a gradient is None once accumulated."""
+    sink = _grad_sink
+    if sink is None or w is None or torch.is_grad_enabled():
         return False, None, None
     wbase = w._base if w._base is not None else w
-    if id(wbase) not in _grad_sink.slots or id(b) not in _grad_sink.slots:
+    if id(wbase) not in sink.slots or (b is not None and id(b) not in sink.slots):
         return False, None, None
-    deferred = _grad_sink.defer
-    wflat, wacc = _grad_sink.take(wbase, deferred)
-    bflat, bacc = _grad_sink.take(b, deferred)
+    deferred = sink.defer
+    wflat, wacc = sink.take(wbase, deferred)
+    bflat, bacc = sink.take(b, deferred) if b is not None else (None, False)
+    dw = wflat.view(w.shape)
     if deferred:
-        conv_group_wgrad_partial(xs, gys, tuple(w.shape), relu_in, _grad_sink, wbase, wflat.view(w.shape), wacc, b, bflat, bacc,
-                                 even_frames=even_frames)
+        src, slab = launch_partial(sink)
+        sink.add_partial(wbase, dw, wacc, b, bflat, bacc, src, slab, w.shape[2] * w.shape[3] * w.shape[4], w.shape[0], w.shape[0] * w.shape[1])
     else:
-        conv_group_wgrad_raw(xs, gys, tuple(w.shape), relu_in, out=wflat.view(w.shape), accum=wacc, dbias=bflat, accum_bias=bacc,
-                             even_frames=even_frames)
-    return True, (None if wacc else wflat.view(w.shape)), (None if bacc else bflat.view(b.shape))
+        launch_direct(dw, wacc, bflat, bacc)
+    return True, (None if wacc else dw), (None if b is None or bacc else bflat.view(b.shape))
 
 
-def _to_sink_w(w, xs, gys, relu_in, even_frames=False):
-    """Weight gradient of one (grouped) convolution into its sink slot, deferred when the sink batches its reductions.
-    Returns (handled, gw) like `_to_sink`."""
-    if _grad_sink is None or w is None or torch.is_grad_enabled():
-        return False, None
-    wbase = w._base if w._base is not None else w
-    if id(wbase) not in _grad_sink.slots:
-        return False, None
-    wflat, wacc = _grad_sink.take(wbase, _grad_sink.defer)
-    if _grad_sink.defer:
-        conv_group_wgrad_partial(xs, gys, tuple(w.shape), relu_in, _grad_sink, wbase, wflat.view(w.shape), wacc, None, None, False,
-                                 even_frames=even_frames)
-    else:
-        conv_group_wgrad_raw(xs, gys, tuple(w.shape), relu_in, out=wflat.view(w.shape), accum=wacc, even_frames=even_frames)
-    return True, (None if wacc else wflat.view(w.shape))
+def _conv_wgrad_to_sink(w, b, xs, gys, relu_in, even_frames=False):
+    """`_wgrad_to_sink` for a (grouped) convolution; with `b` the bias gradient comes out of the same launch
+    (`t2v_conv_wgrad_grouped_bias`: the 3-tap-row kernel sums the dL/dy tiles it stages anyway)."""
+    return _wgrad_to_sink(
+        w, b, lambda sink: _wgrad_partial_launch(xs, gys, tuple(w.shape), relu_in, b is not None, sink, even_frames),
+        lambda dw, wacc, db, bacc: conv_group_wgrad_raw(xs, gys, tuple(w.shape), relu_in, out=dw, accum=wacc, dbias=db, accum_bias=bacc,
+                                                        even_frames=even_frames))
 
 
 def _to_sink(param_like, compute):
@@ -398,37 +392,62 @@ def conv_geom(N, Cin, D, H, W, Cout, kD, kH, kW):
     return g
 
 
-_pack_cache = {}      # id(base parameter) -> {(shape5, tap mask, mode): [weakref, tag, buffer, geom]}
+class _Packed(object):
+    """One persistent packed copy of a parameter (or the block of a fused matrix that one member fills). `ref`: weak reference
+    to the base parameter; `tag`: `_wtag` of the contents `buf` was packed from; `refresh(w)`: re-pack `w` into `buf` in place;
+    `kind`: 'fp32' | 'bf16' | 'fused'; `job`: what `repack_params` puts into its table, without the destination (`buf`) —
+    (src, Cout, Cin, T, taps, mode, dst_rows, dst_cols, row_off, col_off), src None = the live parameter itself (fused members
+    keep the view they were created with)."""
+    __slots__ = ('ref', 'tag', 'buf', 'refresh', 'kind', 'job')
+
+    def __init__(self, base, tag, buf, refresh, kind, job):
+        self.ref, self.tag, self.buf, self.refresh, self.kind, self.job = weakref.ref(base), tag, buf, refresh, kind, job
+
+
+_pack_cache = {}      # id(base parameter) -> {key: _Packed}; key = (shape5, tap mask, mode) | ('bf16', shape5, tap mask, mode) |
+#                       ('fused', key of the fused matrix in `_fused_cache`, member index)
+
+
+def _packed(w5, key, new, args, buf=None):
+    """The packed copy of `w5` filed under `key`: for parameters (2-D convs / Linear arrive as 5-D views of one) PERSISTENT and
+    refreshed in place — lazily here when the parameter changed, eagerly by `repack_params` right after an optimiser step — so
+    that a captured HIP graph always reads the same addresses; anything else (the ggw of a double backward) is packed fresh and
+    not cached. `new(w5, *args)` -> (buffer, refresh, kind, job) makes a copy; `buf`: the shared buffer a fused member must sit in."""
+    base = w5._base if w5._base is not None else w5
+    if not isinstance(base, torch.nn.Parameter):
+        wp, refresh = new(w5, *args)[:2]
+        refresh(w5)
+        return wp
+    tag = _wtag(base, w5.data_ptr())
+    ent = _pack_cache.setdefault(id(base), {})
+    rec = ent.get(key)
+    if rec is not None and rec.ref() is base and (buf is None or rec.buf is buf):
+        if rec.tag != tag:
+            rec.refresh(w5)
+            rec.tag = tag
+        return rec.buf
+    rec = _Packed(base, tag, *new(w5, *args))
+    rec.refresh(w5)
+    ent[key] = rec
+    return rec.buf
+
+
+def _new_packed(w5, ts, mode, bf16):
+    Cout, Cin = w5.shape[0], w5.shape[1]
+    buf = torch.empty((len(ts.taps), Cin * Cout), device=w5.device, dtype=torch.bfloat16 if bf16 else torch.float32)
+    name = 't2v_pack_weight_bf16' if bf16 else 't2v_pack_weight'
+
+    def refresh(w):
+        check(getattr(lib(), name)(_p(w), _p(buf), Cout, Cin, ts.T, ts.taps_c, len(ts.taps), mode, _stream()), name)
+    rows, cols = (Cout, Cin) if mode else (Cin, Cout)
+    if bf16:                                                                 # (bf16-compute layouts: K contiguous)
+        rows, cols = cols, rows
+    return buf, refresh, 'bf16' if bf16 else 'fp32', (None, Cout, Cin, ts.T, list(ts.taps), (2 + mode if bf16 else mode), rows, cols, 0, 0)
 
 
 def packed_weight(w5, geom, mode):
-    """wp[ntaps][Cin][Cout] (mode 0) / wp[ntaps][Cout][Cin] mirrored (mode 1). For parameters the packed
-    buffer is PERSISTENT (one per (parameter, tap set, mode)) and is refreshed in place — lazily here when
-    the parameter changed, eagerly by `repack_params` right after an optimiser step — so that a captured
-    HIP graph always reads the same addresses."""
-    Cout, Cin = w5.shape[0], w5.shape[1]
-    base = w5._base if w5._base is not None else w5          # 2-D convs / Linear arrive as 5-D views
-    cacheable = isinstance(base, torch.nn.Parameter)
-    if not cacheable:
-        wp = torch.empty((len(geom.taps), Cin * Cout), device=w5.device, dtype=torch.float32)
-        check(lib().t2v_pack_weight(_p(w5), _p(wp), Cout, Cin, geom.T, geom.taps_c, len(geom.taps), mode, _stream()),
-              't2v_pack_weight')
-        return wp
-    key = (tuple(w5.shape), geom.mask, mode)
-    tag = _wtag(base, w5.data_ptr())
-    ent = _pack_cache.setdefault(id(base), {})
-    hit = ent.get(key)
-    if hit is not None and hit[0]() is base:
-        if hit[1] != tag:
-            check(lib().t2v_pack_weight(_p(w5), _p(hit[2]), Cout, Cin, geom.T, geom.taps_c, len(geom.taps), mode, _stream()),
-                  't2v_pack_weight')
-            hit[1] = tag
-        return hit[2]
-    wp = torch.empty((len(geom.taps), Cin * Cout), device=w5.device, dtype=torch.float32)
-    check(lib().t2v_pack_weight(_p(w5), _p(wp), Cout, Cin, geom.T, geom.taps_c, len(geom.taps), mode, _stream()),
-          't2v_pack_weight')
-    ent[key] = [weakref.ref(base), tag, wp, geom]
-    return wp
+    """wp[ntaps][Cin][Cout] (mode 0) / wp[ntaps][Cout][Cin] mirrored (mode 1); one per (parameter, tap set, mode), see `_packed`."""
+    return _packed(w5, (tuple(w5.shape), geom.mask, mode), _new_packed, (geom, mode, False))
 
 
 CONV_PRECISION = os.environ.get('T2V_CONV_PRECISION', 'fp32')     # 'bf16': forward / data-gradient GEMMs on bf16 MFMA (fp32 storage
@@ -445,50 +464,18 @@ def set_conv_precision(p):
 
 
 def packed_weight_bf16(w5, ts, mode):
-    """bf16 wpb[ntaps][rows][K] (K contiguous) for the bf16-compute GEMM; persistent per (parameter, tap set, mode) and
-    refreshed lazily when the parameter changed (inside the captured graph under replay)."""
-    Cout, Cin = w5.shape[0], w5.shape[1]
-    base = w5._base if w5._base is not None else w5
-
-    def pack(dst):
-        check(lib().t2v_pack_weight_bf16(_p(w5), _p(dst), Cout, Cin, ts.T, ts.taps_c, len(ts.taps), mode, _stream()),
-              't2v_pack_weight_bf16')
-    if not isinstance(base, torch.nn.Parameter):
-        wp = torch.empty((len(ts.taps), Cin * Cout), device=w5.device, dtype=torch.bfloat16)
-        pack(wp)
-        return wp
-    key = ('bf16', tuple(w5.shape), ts.mask, mode)
-    tag = _wtag(base, w5.data_ptr())
-    ent = _pack_cache.setdefault(id(base), {})
-    hit = ent.get(key)
-    if hit is not None and hit[0]() is base:
-        if hit[1] != tag:
-            pack(hit[2])
-            hit[1] = tag
-        return hit[2]
-    wp = torch.empty((len(ts.taps), Cin * Cout), device=w5.device, dtype=torch.bfloat16)
-    pack(wp)
-    ent[key] = [weakref.ref(base), tag, wp, ts]
-    return wp
+    """bf16 wpb[ntaps][rows][K] (K contiguous) for the bf16-compute GEMM; one per (parameter, tap set, mode), see `_packed`
+    (under replay the lazy refresh sits inside the captured graph)."""
+    return _packed(w5, ('bf16', tuple(w5.shape), ts.mask, mode), _new_packed, (ts, mode, True))
 
 
 _repack_tables = {}
 
 
-def _pack_job_of(p, key, hit):
-    """(src, dst, Cout, Cin, T, taps, mode, dst_rows, dst_cols, row_off, col_off) of one cached packed variant."""
-    if callable(hit[3]):
-        return hit[4]                    # member of a fused matrix: its job tuple was recorded at creation
-    if key[0] == 'bf16':                 # bf16-compute layouts: pack_multi modes 2 (forward) / 3 (data gradient)
-        _, shape5, _, mode = key
-        ts = hit[3]
-        Cout, Cin = shape5[0], shape5[1]
-        src = p if tuple(p.shape) == tuple(shape5) else p.view(shape5)
-        return (src, hit[2], Cout, Cin, ts.T, list(ts.taps), 2 + mode, (Cin if mode else Cout), (Cout if mode else Cin), 0, 0)
-    shape5, _, mode = key
-    geom = hit[3]
-    Cout, Cin = shape5[0], shape5[1]
-    return (p, hit[2], Cout, Cin, geom.T, list(geom.taps), mode, (Cout if mode else Cin), (Cin if mode else Cout), 0, 0)
+def _pack_job_of(p, rec):
+    """(src, dst, Cout, Cin, T, taps, mode, dst_rows, dst_cols, row_off, col_off) of one cached packed variant of parameter `p`
+    (bf16-compute layouts: pack_multi modes 2 (forward) / 3 (data gradient))."""
+    return (p if rec.job[0] is None else rec.job[0], rec.buf) + rec.job[1:]
 
 
 def pack_job_groups(T, ntaps, mode):
@@ -509,20 +496,20 @@ def repack_params(params):
         ent = _pack_cache.get(id(p))
         if not ent:
             continue
-        for key, hit in ent.items():
-            if hit[0]() is p:
-                jobs.append((p, key, hit))
+        for key, rec in ent.items():
+            if rec.ref() is p:
+                jobs.append((p, key, rec))
     if not jobs:
         return
-    sig = tuple((id(p), key, hit[2].data_ptr(), p.data_ptr()) for p, key, hit in jobs)
+    sig = tuple((id(p), key, rec.buf.data_ptr(), p.data_ptr()) for p, key, rec in jobs)
     tkey = tuple(id(p) for p in params)
     tab = _repack_tables.get(tkey)
     if tab is None or tab[0] != sig:
         assert C.sizeof(PackJob) == lib().t2v_pack_job_bytes()
         arr = (PackJob * len(jobs))()
         blocks = 0
-        for a, (p, key, hit) in zip(arr, jobs):
-            src, dst, Cout, Cin, T, taps, mode, rows, cols, ro, co = _pack_job_of(p, key, hit)
+        for a, (p, key, rec) in zip(arr, jobs):
+            src, dst, Cout, Cin, T, taps, mode, rows, cols, ro, co = _pack_job_of(p, rec)
             a.src, a.dst = src.data_ptr(), dst.data_ptr()
             a.Cout, a.Cin, a.T, a.ntaps, a.mode = Cout, Cin, T, len(taps), mode
             a.dst_rows, a.dst_cols, a.row_off, a.col_off = rows, cols, ro, co
@@ -536,52 +523,44 @@ def repack_params(params):
         tab = (sig, dev, len(jobs), blocks)
         _repack_tables[tkey] = tab
     check(lib().t2v_pack_multi(_p(tab[1]), tab[2], tab[3], _stream()), 't2v_pack_multi')
-    for p, key, hit in jobs:
-        hit[1] = _wtag(p)
-    for fkey, fh in _fused_cache.items():
-        if any(r() is p for r in fh[0] for p in params):
-            fh[1] = tuple(_wtag(w()) for w in fh[0] if w() is not None)      # members are whole-parameter views: same pointer
+    for p, key, rec in jobs:               # (members of fused matrices included: they are whole-parameter views, same pointer)
+        rec.tag = _wtag(p)
 
 
-_fused_cache = {}
+_fused_cache = {}     # (ids of the base parameters, shape5, tap mask, mode) -> (weak references to them, the shared buffer); the
+#                       members' `_Packed` records (tags, refresh, repack jobs) are in `_pack_cache`
+
+
+def _new_fused_member(w, ts, mode, wp, n, i):
+    Cout, Cin = w.shape[0], w.shape[1]
+    rows, cols, ro, co = (Cin, n * Cout, 0, i * Cout) if mode == 0 else (n * Cout, Cin, i * Cout, 0)
+    m = mode | (8 if is_tap_major(w) else 0)          # (mode | 8: the source is stored tap-major)
+
+    def refresh(wi):
+        check(lib().t2v_pack_weight_into(_p(wi), _p(wp), Cout, Cin, ts.T, ts.taps_c, len(ts.taps), m, rows, cols, ro, co, _stream()),
+              't2v_pack_weight_into')
+    return wp, refresh, 'fused', (w, Cout, Cin, ts.T, list(ts.taps), m, rows, cols, ro, co)
 
 
 def packed_fused(ws, ts, mode):
     """ONE packed matrix for several same-shape weights applied to the same input (mode 0: outputs side by
     side -> wp[tap][Cin][n*Cout]) or whose data gradients add up (mode 1: wp[tap][n*Cout][Cin]).
-    Persistent and refreshed per member exactly like `packed_weight` (the members usually arrive as 5-D views of the
-    parameters: the cache is keyed by the parameters behind them)."""
+    Persistent, and each member's block refreshed, exactly like `packed_weight` (the members usually arrive as 5-D views of the
+    parameters: the cache is keyed by the parameters behind them, which is also where `repack_params` finds the members)."""
     n = len(ws)
-    Cout, Cin = ws[0].shape[0], ws[0].shape[1]
     bases = [w._base if w._base is not None else w for w in ws]
     cacheable = all(isinstance(b_, torch.nn.Parameter) for b_ in bases)
     key = (tuple(id(b_) for b_ in bases), tuple(ws[0].shape), ts.mask, mode)
-    hit = _fused_cache.get(key) if cacheable else None
-    if hit is not None and all(r() is b_ for r, b_ in zip(hit[0], bases)):
-        tag = tuple(_wtag(b_, w.data_ptr()) for b_, w in zip(bases, ws))
-        if hit[1] != tag:
-            for i, w in enumerate(ws):
-                hit[3][i](w)
-            hit[1] = tag
-        return hit[2]
-    rows, cols = (Cin, n * Cout) if mode == 0 else (n * Cout, Cin)
-    wp = torch.empty((len(ts.taps), rows * cols), device=ws[0].device, dtype=torch.float32)
-    refresh = []
+    refs, wp = _fused_cache.get(key, (None, None)) if cacheable else (None, None)
+    if wp is None or any(r() is not b_ for r, b_ in zip(refs, bases)):
+        wp = torch.empty((len(ts.taps), n * ws[0].shape[0] * ws[0].shape[1]), device=ws[0].device, dtype=torch.float32)
+        if cacheable:
+            _fused_cache[key] = ([weakref.ref(b_) for b_ in bases], wp)
     for i, w in enumerate(ws):
-        ro, co = (0, i * Cout) if mode == 0 else (i * Cout, 0)
-
-        tm = 8 if is_tap_major(w) else 0         # (mode | 8: the source is stored tap-major)
-
-        def fn(wi, ro=ro, co=co, tm=tm):
-            check(lib().t2v_pack_weight_into(_p(wi), _p(wp), Cout, Cin, ts.T, ts.taps_c, len(ts.taps), mode | tm, rows, cols,
-                                             ro, co, _stream()), 't2v_pack_weight_into')
-        refresh.append(fn)
-        fn(w)
-        if cacheable:                      # lets `repack_params` refresh this member in its one multi-tensor launch
-            _pack_cache.setdefault(id(bases[i]), {})[('fused', key, i)] = [weakref.ref(bases[i]), _wtag(bases[i], w.data_ptr()), wp, fn,
-                                                                           (w, wp, Cout, Cin, ts.T, list(ts.taps), mode | tm, rows, cols, ro, co)]
-    if cacheable:
-        _fused_cache[key] = [[weakref.ref(b_) for b_ in bases], tuple(_wtag(b_, w.data_ptr()) for b_, w in zip(bases, ws)), wp, refresh]
+        if cacheable:
+            _packed(w, ('fused', key, i), _new_fused_member, (ts, mode, wp, n, i), wp)
+        else:
+            _new_fused_member(w, ts, mode, wp, n, i)[1](w)
     return wp
 
 
@@ -1296,7 +1275,7 @@ class ConvLSTMFn(Function):
             gin = gpre[1:].reshape((steps - 1) * B, 4 * Cc, 1, h, w)
             gwh4 = conv_group_wgrad_raw([hin], [gin], w4shape)
         else:
-            gwh4 = _zeros_like(gwx4)
+            gwh4 = zeros_like(gwx4)
         gwx = [gwx4[g * Cc:(g + 1) * Cc].squeeze(2) for g in range(4)]
         gwh = [gwh4[g * Cc:(g + 1) * Cc].squeeze(2) for g in range(4)]
         return (gx, None) + tuple(gwx) + tuple(gbx) + tuple(gwh)
@@ -1825,9 +1804,9 @@ _transposed_cache = {}
 def transposed_weight(w):
     """w^T of a 2-D parameter as a dense tensor, cached until the parameter changes (same tags as the packed conv weights)."""
     tag = _wtag(w)
-    hit = _transposed_cache.get(id(w))
-    if hit is not None and hit[0]() is w and hit[1] == tag:
-        return hit[2]
+    ref, old, wt = _transposed_cache.get(id(w), (None, None, None))
+    if ref is not None and ref() is w and old == tag:
+        return wt
     wt = _permute_01(_c(w.detach()), w.shape[0], w.shape[1], 1).view(w.shape[1], w.shape[0])
     _transposed_cache[id(w)] = (weakref.ref(w), tag, wt)
     return wt
@@ -1858,7 +1837,7 @@ def lstm_encode(tokens, lengths, embed_weight, lstm, hidden_size, num_layers, bi
         check(lib().t2v_gather_rows(_p(_c(embed_weight.detach())), _p(tok), _p(x), B * L, E, 0, _stream()), 't2v_gather_rows')
         h_n = torch.empty((num_layers * D, B, H), device=dev, dtype=torch.float32)
         c_n = torch.empty((num_layers * D, B, H), device=dev, dtype=torch.float32)
-        zero = _zeros_like(h_n[0])
+        zero = zeros_like(h_n[0])
         inp = x                                                   # [B*L, In]
         for layer in range(num_layers):
             out = torch.empty((B, L, D * H), device=dev, dtype=torch.float32)
@@ -1943,8 +1922,8 @@ class LstmDirFn(Function):
         B, L, H = hprev.shape
         H4 = 4 * H
         dev = hprev.device
-        DH = _c(d_hn).clone() if d_hn is not None else _zeros_like(c_n)
-        DC = _c(d_cn).clone() if d_cn is not None else _zeros_like(c_n)
+        DH = _c(d_hn).clone() if d_hn is not None else zeros_like(c_n)
+        DC = _c(d_cn).clone() if d_cn is not None else zeros_like(c_n)
         d_out = _c(d_out) if d_out is not None else None
         dG = torch.empty((B, L, H4), device=dev, dtype=torch.float32)
         for s_ in range(L - 1, -1, -1):
@@ -2227,6 +2206,19 @@ def _fwd_workspace(arr, n, cin, cout, device):
     return torch.empty((nws,), device=device, dtype=torch.float32) if nws > 0 else None
 
 
+def _launch_group_fwd(arr, n, cin, cout, w5, ts, mode, bias, ws, flags, bf16=None):
+    """One grouped forward / data-gradient launch on the packed copy of `w5` for tap set `ts`: the bf16-compute GEMM when that
+    mode is on and the library has a bf16 kernel for this table (`bf16`: the answer, where the caller has asked already), else fp32."""
+    if bf16 is None:
+        bf16 = CONV_PRECISION == 'bf16' and lib().t2v_conv_fwd_grouped_bf16_ok(arr, n, cin, cout)
+    if bf16:
+        wp = packed_weight_bf16(w5, ts, mode)
+        check(lib().t2v_conv_fwd_grouped_bf16(arr, n, cin, cout, _p(wp), _p(bias), _p(ws), flags, _stream()), 't2v_conv_fwd_grouped_bf16')
+    else:
+        wp = packed_weight(w5, ts, mode)
+        check(lib().t2v_conv_fwd_grouped(arr, n, cin, cout, _p(wp), _p(bias), _p(ws), flags, _stream()), 't2v_conv_fwd_grouped')
+
+
 def conv_group_raw(xs5, w5, bias=None, relu_in=False, mode=0, masks=None, outs=None, accum=False, even_frames=False):
     """mode 0: ys[i] = conv(xs[i], w) (+bias); mode 1: data gradient (xs are dL/dy, channels swap roles).
     masks: ys[i] is zeroed where masks[i] <= 0 (the ReLU adjoint, fused into the epilogue)."""
@@ -2248,13 +2240,7 @@ def conv_group_raw(xs5, w5, bias=None, relu_in=False, mode=0, masks=None, outs=N
     ws = _fwd_workspace(arr, len(xs5), cin, cout, xs5[0].device)
     flags = ((FLAG_BIAS if bias is not None else 0) | (FLAG_RELU_IN if relu_in else 0) | (FLAG_MASK_OUT if masks is not None else 0) |
              (FLAG_ACCUM if accum else 0))
-    if CONV_PRECISION == 'bf16' and lib().t2v_conv_fwd_grouped_bf16_ok(arr, len(xs5), cin, cout):
-        wpb = packed_weight_bf16(w5, ts, mode)
-        check(lib().t2v_conv_fwd_grouped_bf16(arr, len(xs5), cin, cout, _p(wpb), _p(bias), _p(ws), flags, _stream()),
-              't2v_conv_fwd_grouped_bf16')
-        return ys
-    wp = packed_weight(w5, ts, mode)
-    check(lib().t2v_conv_fwd_grouped(arr, len(xs5), cin, cout, _p(wp), _p(bias), _p(ws), flags, _stream()), 't2v_conv_fwd_grouped')
+    _launch_group_fwd(arr, len(xs5), cin, cout, w5, ts, mode, bias, ws, flags)
     return ys
 
 
@@ -2304,14 +2290,6 @@ def _wgrad_partial_launch(xs5, gys5, wshape, relu_in, want_bias, sink=None, even
     return src, slab
 
 
-def conv_group_wgrad_partial(xs5, gys5, wshape, relu_in, sink, wbase, dw, wacc, b, dbias, bacc, even_frames=False):
-    """The weight-gradient launch WITHOUT its reduce pass: the k-split partial sums stay in a slab that `sink` keeps alive
-    and sums (with every other pending slab) in its one `flush()` launch."""
-    src, slab = _wgrad_partial_launch(xs5, gys5, wshape, relu_in, b is not None, sink, even_frames)
-    k = tuple(wshape[2:])
-    sink.add_partial(wbase, dw, wacc, b, dbias, bacc, src, slab, k[0] * k[1] * k[2], wshape[0], wshape[0] * wshape[1])
-
-
 def _fused_gates_to_sink(sink, gates, x5, gy5, w4shape):
     """Weight gradients of the ConvLSTM's four gates (ONE launch on the side-by-side [4C, C, ...] weight) straight into the
     gates' tap-major sink slots: each gate is a row block of every slab plane. Returns the four gradient views."""
@@ -2326,12 +2304,6 @@ def _fused_gates_to_sink(sink, gates, x5, gy5, w4shape):
         sg.slab = src.slab + 4 * g * Cc * Cc                      # rows [g*C, (g+1)*C) of each [4C][C] plane
         sink.add_partial(w, flat, acc, None, None, False, sg, slab, T, Cc, Cc * Cc, tap_major=True)
         out.append(None if acc else flat.as_strided(w.shape, w.stride()))
-    return out
-
-
-def _zeros_like(t):
-    out = torch.empty_like(t)
-    check(lib().t2v_fill(_p(out), 0.0, out.numel(), _stream()), 't2v_fill')
     return out
 
 
@@ -2372,37 +2344,43 @@ class ConvG(Function):
     def backward(ctx, *gys):
         saved = ctx.saved_tensors
         w, xs = saved[0], saved[1:]
-        live = [i for i, g in enumerate(gys) if g is not None]
-        gxs = [None] * len(xs)
+        live = _live(gys)
         gw = gb = None
         if not live:
-            return (None, None, None) + tuple(gxs)
-        need = [i for i in live if ctx.needs_input_grad[3 + i]]
-        if need:
-            if ctx.relu_in:
-                res = ConvDgradMaskG.apply(w, len(need), *([gys[i] for i in need] + [xs[i] for i in need]))
-            else:
-                res = ConvDgradG.apply(w, *[gys[i] for i in need])
-            for i, r in zip(need, res):
-                gxs[i] = r
+            return (None, None, None) + (None,) * len(xs)
+        gxs = _dgrad_group(w, ctx.relu_in, gys, xs, [i for i in live if ctx.needs_input_grad[3 + i]])
         if _param_grads_enabled:
             gw, gb = _group_param_grads(w, ctx.bias if ctx.has_bias else None, ctx.relu_in, [xs[i] for i in live],
                                         [gys[i] for i in live], ctx.needs_input_grad[0], ctx.has_bias and ctx.needs_input_grad[1])
         return (gw, gb, None) + tuple(gxs)
 
 
+def _dgrad_group(w, relu, gys, xs, idx):
+    """Data gradients of the members `idx` of a grouped convolution in one launch, with the ReLU adjoint [xs > 0] in the
+    epilogue when `relu`: a list as long as `gys`, None for every other member."""
+    if not idx:
+        return [None] * len(gys)
+    g = [gys[i] for i in idx]
+    res = ConvDgradMaskG.apply(w, len(idx), *(g + [xs[i] for i in idx])) if relu else ConvDgradG.apply(w, *g)
+    return _scatter(len(gys), idx, res)
+
+
+def _group_wgrad(w, lx, lg, relu_in):
+    """Weight gradient of a grouped convolution: into the gradient sink when one is armed, else as a differentiable Function."""
+    done, gw, _ = _conv_wgrad_to_sink(w, None, lx, lg, relu_in)
+    return gw if done else ConvWgradG.apply(tuple(w.shape), relu_in, len(lx), *(lx + lg))
+
+
 def _group_param_grads(w, b, relu_in, lx, lg, need_w, need_b):
     """(gw, gb) of a grouped convolution over its live members: into the gradient sink when one is armed (one launch for
-    both when possible), else as differentiable Functions."""
+    both when both have slots), else as differentiable Functions."""
     gw = gb = None
     both = False
     if need_w and need_b:
-        both, gw, gb = _to_sink_wb(w, b, lx, lg, relu_in)
+        both, gw, gb = _conv_wgrad_to_sink(w, b, lx, lg, relu_in)
     if not both:
         if need_w:
-            done, gw = _to_sink_w(w, lx, lg, relu_in)
-            if not done:
-                gw = ConvWgradG.apply(tuple(w.shape), relu_in, len(lx), *(lx + lg))
+            gw = _group_wgrad(w, lx, lg, relu_in)
         if need_b:
             done, gb = _to_sink(b, lambda out, acc: channel_sum_group_raw(lg, out=out, accum=acc))
             if not done:
@@ -2469,14 +2447,8 @@ def _dgrad_even_frames_raw(gys, w5, masks, plan_only=False):
         launches.append((arr, len(mem)))
     if plan_only:
         return True
-    if bf16:
-        wpb = packed_weight_bf16(w5, ts, 1)
-        for arr, n in launches:
-            check(lib().t2v_conv_fwd_grouped_bf16(arr, n, Cout, Cin, _p(wpb), None, None, FLAG_MASK_OUT, _stream()), 't2v_conv_fwd_grouped_bf16')
-        return outs
-    wp = packed_weight(w5, ts, 1)
-    for arr, n in launches:
-        check(lib().t2v_conv_fwd_grouped(arr, n, Cout, Cin, _p(wp), None, None, FLAG_MASK_OUT, _stream()), 't2v_conv_fwd_grouped')
+    for arr, n in launches:                        # (every launch was asked above: bf16 mode means the bf16 kernel for each)
+        _launch_group_fwd(arr, n, Cout, Cin, w5, ts, 1, None, None, FLAG_MASK_OUT, bf16)
     return outs
 
 
@@ -2501,22 +2473,21 @@ class ConvDgradEvenMaskG(Function):
         saved = ctx.saved_tensors
         n = ctx.n
         w, gys, xs = saved[0], saved[1:1 + n], saved[1 + n:]
-        live = [i for i, g in enumerate(ggxs) if g is not None]
+        live = _live(ggxs)
         d_w = None
         d_gys = [None] * n
         if live:
             hs = dict(zip(live, ReluMaskG.apply(len(live), *([ggxs[i] for i in live] + [xs[i] for i in live]))))
             if ctx.needs_input_grad[0] and _param_grads_enabled:
                 lx, lg = [hs[i] for i in live], [gys[i] for i in live]
-                done, d_w = _to_sink_w(w, lx, lg, False, even_frames=True)
+                done, d_w, _ = _conv_wgrad_to_sink(w, None, lx, lg, False, even_frames=True)
                 if not done:          # no sink (or a graph is being recorded): through the zero-stuffed gradient
                     cfg = ((1, 1, 1), (2, 1, 1), (0, 0, 0))
                     full = AvgPool3dBwdG.apply(tuple(cfg for _ in live), tuple(tuple(xs[i].shape[2:]) for i in live), *lg)
                     d_w = ConvWgradG.apply(tuple(w.shape), False, len(live), *(lx + list(full)))
             need = [i for i in live if ctx.needs_input_grad[2 + i]]
             if need:
-                for i, r in zip(need, ConvEvenFramesG.apply(w, None, False, *[hs[i] for i in need])):
-                    d_gys[i] = r
+                d_gys = _scatter(n, need, ConvEvenFramesG.apply(w, None, False, *[hs[i] for i in need]))
         return (d_w, None) + tuple(d_gys) + (None,) * n
 
 
@@ -2537,19 +2508,15 @@ class ConvEvenFramesG(Function):
     def backward(ctx, *gys):
         saved = ctx.saved_tensors
         w, xs = saved[0], saved[1:]
-        live = [i for i, g in enumerate(gys) if g is not None]
-        gxs = [None] * len(xs)
+        live = _live(gys)
         gw = gb = None
         if not live:
-            return (None, None, None) + tuple(gxs)
+            return (None, None, None) + (None,) * len(xs)
         need = [i for i in live if ctx.needs_input_grad[3 + i]]
         fast = None
         if need and ctx.relu_in and not torch.is_grad_enabled():
             # no graph is being recorded: the data gradient straight from the even-frame gradients (two strided-output launches)
             fast = _dgrad_even_frames_raw([gys[i] for i in need], w, [xs[i] for i in need])
-            if fast is not None:
-                for i, r in zip(need, fast):
-                    gxs[i] = r
         gfull = [None] * len(xs)
 
         def full_frames():
@@ -2563,28 +2530,18 @@ class ConvEvenFramesG(Function):
         if need and fast is None and ctx.relu_in and torch.is_grad_enabled() and \
                 _dgrad_even_frames_raw([gys[i] for i in need], w, [xs[i] for i in need], plan_only=True):
             # a graph is being recorded (gradient penalty): the same two launches as a differentiable Function
-            res = ConvDgradEvenMaskG.apply(w, len(need), *([gys[i] for i in need] + [xs[i] for i in need]))
-            for i, r in zip(need, res):
-                gxs[i] = r
-            fast = res
+            fast = ConvDgradEvenMaskG.apply(w, len(need), *([gys[i] for i in need] + [xs[i] for i in need]))
         if need and fast is None:
-            full_frames()
-            if ctx.relu_in:
-                res = ConvDgradMaskG.apply(w, len(need), *([gfull[i] for i in need] + [xs[i] for i in need]))
-            else:
-                res = ConvDgradG.apply(w, *[gfull[i] for i in need])
-            for i, r in zip(need, res):
-                gxs[i] = r
+            gxs = _dgrad_group(w, ctx.relu_in, full_frames(), xs, need)
+        else:
+            gxs = _scatter(len(xs), need, fast or ())
         if _param_grads_enabled:
             need_w, need_b = ctx.needs_input_grad[0], ctx.has_bias and ctx.needs_input_grad[1]
             lx, lg = [xs[i] for i in live], [gys[i] for i in live]
             done = False
             if need_w and not torch.is_grad_enabled() and w.shape[1] >= 64 and w.shape[4] == 3 and any(t.shape[4] > 1 for t in lx):
                 # gradient sink armed: the weight-gradient kernel reads dL/dy on the even frames as it is (half the voxels)
-                if need_b:
-                    done, gw, gb = _to_sink_wb(w, ctx.bias, lx, lg, ctx.relu_in, even_frames=True)
-                else:
-                    done, gw = _to_sink_w(w, lx, lg, ctx.relu_in, even_frames=True)
+                done, gw, gb = _conv_wgrad_to_sink(w, ctx.bias if need_b else None, lx, lg, ctx.relu_in, even_frames=True)
             if not done:
                 full_frames()
                 gw, gb = _group_param_grads(w, ctx.bias if ctx.has_bias else None, ctx.relu_in, lx, [gfull[i] for i in live], need_w, need_b)
@@ -2634,27 +2591,21 @@ class ConvMultiG(Function):
             fresh = [i for i in mem if gxs[i] is None]
             again = [i for i in mem if gxs[i] is not None]
             if fresh:
-                if relus[k]:
-                    res = ConvDgradMaskG.apply(ws[k], len(fresh), *([g_of[k][i] for i in fresh] + [xs[i] for i in fresh]))
-                else:
-                    res = ConvDgradG.apply(ws[k], *[g_of[k][i] for i in fresh])
-                for i, r in zip(fresh, res):
-                    gxs[i] = r
+                res = _dgrad_group(ws[k], relus[k], g_of[k], xs, fresh)
+                for i in fresh:
+                    gxs[i] = res[i]
             if again:
                 if fused and not relus[k]:
                     conv_group_raw([g_of[k][i] for i in again], ws[k], None, False, 1, outs=[gxs[i] for i in again], accum=True)
                 else:
-                    if relus[k]:
-                        res = ConvDgradMaskG.apply(ws[k], len(again), *([g_of[k][i] for i in again] + [xs[i] for i in again]))
-                    else:
-                        res = ConvDgradG.apply(ws[k], *[g_of[k][i] for i in again])
+                    res = _dgrad_group(ws[k], relus[k], g_of[k], xs, again)
                     # (recorded backward: one grouped add for all members instead of one launch per member)
-                    for i, t in zip(again, AddG.apply(*([gxs[i] for i in again] + list(res)))):
+                    for i, t in zip(again, AddG.apply(*([gxs[i] for i in again] + [res[i] for i in again]))):
                         gxs[i] = t
         grads = []
         for k in range(nspec):
             gw = gb = None
-            live = [i for i in range(n) if g_of[k][i] is not None]
+            live = _live(g_of[k])
             if live and _param_grads_enabled:
                 gw, gb = _group_param_grads(ws[k], bs[k], relus[k], [xs[i] for i in live], [g_of[k][i] for i in live],
                                             ctx.needs_input_grad[2 + 2 * k], bs[k] is not None and ctx.needs_input_grad[3 + 2 * k])
@@ -2683,21 +2634,16 @@ class ConvDgradG(Function):
     def backward(ctx, *ggxs):
         saved = ctx.saved_tensors
         w, gys = saved[0], saved[1:]
-        live = [i for i, g in enumerate(ggxs) if g is not None]
+        live = _live(ggxs)
         d_w = None
         d_gys = [None] * len(gys)
         if not live:
             return (None,) + tuple(d_gys)
         if ctx.needs_input_grad[0] and _param_grads_enabled:
-            lx, lg = [ggxs[i] for i in live], [gys[i] for i in live]
-            done, d_w = _to_sink_w(w, lx, lg, False)
-            if not done:
-                d_w = ConvWgradG.apply(tuple(w.shape), False, len(live), *(lx + lg))
+            d_w = _group_wgrad(w, [ggxs[i] for i in live], [gys[i] for i in live], False)
         need = [i for i in live if ctx.needs_input_grad[1 + i]]
         if need:
-            res = ConvG.apply(w, None, False, *[ggxs[i] for i in need])
-            for i, r in zip(need, res):
-                d_gys[i] = r
+            d_gys = _scatter(len(gys), need, ConvG.apply(w, None, False, *[ggxs[i] for i in need]))
         return (d_w,) + tuple(d_gys)
 
 
@@ -2719,7 +2665,7 @@ class ConvDgradMaskG(Function):
         saved = ctx.saved_tensors
         n = ctx.n
         w, gys, xs = saved[0], saved[1:1 + n], saved[1 + n:]
-        live = [i for i, g in enumerate(ggxs) if g is not None]
+        live = _live(ggxs)
         d_w = None
         d_gys = [None] * n
         if live:
@@ -2728,15 +2674,10 @@ class ConvDgradMaskG(Function):
             else:
                 hs = {i: ReluMask.apply(ggxs[i], xs[i]) for i in live}
             if ctx.needs_input_grad[0] and _param_grads_enabled:
-                lx, lg = [hs[i] for i in live], [gys[i] for i in live]
-                done, d_w = _to_sink_w(w, lx, lg, False)
-                if not done:
-                    d_w = ConvWgradG.apply(tuple(w.shape), False, len(live), *(lx + lg))
+                d_w = _group_wgrad(w, [hs[i] for i in live], [gys[i] for i in live], False)
             need = [i for i in live if ctx.needs_input_grad[2 + i]]
             if need:
-                res = ConvG.apply(w, None, False, *[hs[i] for i in need])
-                for i, r in zip(need, res):
-                    d_gys[i] = r
+                d_gys = _scatter(n, need, ConvG.apply(w, None, False, *[hs[i] for i in need]))
         return (d_w, None) + tuple(d_gys) + (None,) * n
 
 
@@ -2755,18 +2696,14 @@ class ConvWgradG(Function):
         wshape, relu_in, n = ctx.cfg
         saved = ctx.saved_tensors
         xs, gys = saved[:n], saved[n:]
-        d_xs = [None] * n
         d_gys = [None] * n
         need_x = [i for i in range(n) if ctx.needs_input_grad[3 + i]]
-        if need_x:
-            res = ConvDgradG.apply(ggw, *[gys[i] for i in need_x])
-            for i, r in zip(need_x, res):
-                d_xs[i] = ReluMask.apply(r, xs[i]) if relu_in else r
+        d_xs = _dgrad_group(ggw, False, gys, xs, need_x)
+        if relu_in:
+            d_xs = [None if r is None else ReluMask.apply(r, x) for r, x in zip(d_xs, xs)]
         need_g = [i for i in range(n) if ctx.needs_input_grad[3 + n + i]]
         if need_g:
-            res = ConvG.apply(ggw, None, relu_in, *[xs[i] for i in need_g])
-            for i, r in zip(need_g, res):
-                d_gys[i] = r
+            d_gys = _scatter(n, need_g, ConvG.apply(ggw, None, relu_in, *[xs[i] for i in need_g]))
         return (None, None, None) + tuple(d_xs) + tuple(d_gys)
 
 
@@ -2838,7 +2775,7 @@ def _pass_none_through(cls):
 from .functional_pool import (pool_conv_ok, pool_conv_group, pool_tmode, PoolConvG, PoolConvDgradG, PoolConvWgradG, boxsum_raw, unbox_raw,     # noqa: E402,F401
                               pool_fwd_raw, pool_dgrad_raw, pool_wgrad_raw, up_conv, up_conv_ok, UpConvFn)
 # the projection head of the text-conditioned discriminator (opt-in): functional_proj.py
-from .functional_proj import (proj_rows_group, proj_rows_raw, proj_feat_raw, proj_cond_raw, proj_weight_raw, ProjRowsG, ProjFeatG,     # noqa: E402,F401
+from .functional_proj import (_scatter, proj_rows_group, proj_rows_raw, proj_feat_raw, proj_cond_raw, proj_weight_raw, ProjRowsG, ProjFeatG,     # noqa: E402,F401
                               ProjCondG, ProjWeightG)
 # the minibatch standard deviation head of the discriminator (opt-in): functional_mbstd.py
 from .functional_mbstd import check_group as mbstd_check_group  # noqa: E402,F401

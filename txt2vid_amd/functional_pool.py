@@ -217,33 +217,27 @@ def pool_wgrad_raw(rts, gzs, shapes, tmodes, wshape, out=None, accum=False, dbia
     return dw
 
 
-def _pool_wgrad_to_sink(w, b, rts, gzs, shapes, tmodes, need_b):
-    """Weight (and bias) gradient into the gradient sink's slots, deferred like `functional.conv_group_wgrad_partial` when the sink
-    batches its reductions. Returns (handled, gw, gb)."""
-    TF = _TF()
-    sink = TF._grad_sink
-    if sink is None or torch.is_grad_enabled():
-        return False, None, None
-    wbase = w._base if w._base is not None else w
-    if id(wbase) not in sink.slots or (need_b and id(b) not in sink.slots):
-        return False, None, None
+def _pool_wgrad_partial(sink, rts, gzs, shapes, tmodes, wshape, want_bias):
+    """The pooled weight-gradient main kernel alone, its k-split partial sums in a slab of `sink`: (WgradSrc, slab)."""
     gzs = [_c(g) for g in gzs]
-    cout, cin = w.shape[0], w.shape[1]
-    wflat, wacc = sink.take(wbase, sink.defer)
-    bflat, bacc = sink.take(b, sink.defer) if need_b else (None, False)
-    if sink.defer:
-        arr = _wgrad_table(rts, gzs, shapes, tmodes)
-        n = int(lib().t2v_pool_conv_wgrad_slab_floats(arr, len(rts), cin, cout, 3, 1 if need_b else 0))
-        if n <= 0:
-            raise RuntimeError('bad pooled weight-gradient geometry')
-        slab = sink.alloc_slab(n, rts[0].device)
-        src = WgradSrc()
-        check(lib().t2v_pool_conv_wgrad_partial(arr, len(rts), cin, cout, 3, _p(slab), 1 if need_b else 0, 0, C.byref(src),
-                                                TF._side.fork(rts, gzs)), 't2v_pool_conv_wgrad_partial')
-        sink.add_partial(wbase, wflat.view(w.shape), wacc, b if need_b else None, bflat, bacc, src, slab, 27, cout, cout * cin)
-    else:
-        pool_wgrad_raw(rts, gzs, shapes, tmodes, tuple(w.shape), out=wflat.view(w.shape), accum=wacc, dbias=bflat, accum_bias=bacc)
-    return True, (None if wacc else wflat.view(w.shape)), ((None if bacc else bflat.view(b.shape)) if need_b else None)
+    cout, cin, kD = wshape[0], wshape[1], wshape[2]
+    arr = _wgrad_table(rts, gzs, shapes, tmodes)
+    n = int(lib().t2v_pool_conv_wgrad_slab_floats(arr, len(rts), cin, cout, kD, 1 if want_bias else 0))
+    if n <= 0:
+        raise RuntimeError('bad pooled weight-gradient geometry')
+    slab = sink.alloc_slab(n, rts[0].device)
+    src = WgradSrc()
+    check(lib().t2v_pool_conv_wgrad_partial(arr, len(rts), cin, cout, kD, _p(slab), 1 if want_bias else 0, 0, C.byref(src),
+                                            _TF()._side.fork(rts, gzs)), 't2v_pool_conv_wgrad_partial')
+    return src, slab
+
+
+def _pool_wgrad_to_sink(w, b, rts, gzs, shapes, tmodes):
+    """Weight (and, with `b`, bias) gradient into the gradient sink's slots (`functional._wgrad_to_sink`, which defers the
+    reduce when the sink batches its reductions). Returns (handled, gw, gb)."""
+    return _TF()._wgrad_to_sink(
+        w, b, lambda sink: _pool_wgrad_partial(sink, rts, gzs, shapes, tmodes, tuple(w.shape), b is not None),
+        lambda dw, wacc, db, bacc: pool_wgrad_raw(rts, gzs, shapes, tmodes, tuple(w.shape), out=dw, accum=wacc, dbias=db, accum_bias=bacc))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -286,7 +280,7 @@ class PoolConvG(Function):
             if need_w:
                 lr, lg = [rts[i] for i in live], [gzs[i] for i in live]
                 lsh, ltm = [shapes[i] for i in live], [tmodes[i] for i in live]
-                done, gw, gb = _pool_wgrad_to_sink(w, b, lr, lg, lsh, ltm, need_b)
+                done, gw, gb = _pool_wgrad_to_sink(w, b if need_b else None, lr, lg, lsh, ltm)
                 if not done:
                     gw = PoolConvWgradG.apply(tuple(w.shape), tuple(ltm), tuple(lsh), len(live), *(lr + lg))
                     if need_b:
@@ -336,7 +330,7 @@ class PoolConvDgradG(Function):
                 for i, r in zip(need, res):
                     d_gzs[i] = r
             if want_w:
-                done, d_w, _ = _pool_wgrad_to_sink(w, None, rts, [gzs[i] for i in live], lsh, ltm, False)
+                done, d_w, _ = _pool_wgrad_to_sink(w, None, rts, [gzs[i] for i in live], lsh, ltm)
                 if not done:
                     d_w = pool_wgrad_raw(rts, [gzs[i] for i in live], lsh, ltm, tuple(w.shape))
         else:
