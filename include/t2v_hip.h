@@ -904,6 +904,38 @@ int t2v_prdc_counts(const float* X, const float* Y, int n, int d, int k, const d
                     void* ws, void* stream);
 size_t t2v_prdc_counts_ws_bytes(int n, int d, int k);
 
+/* ---- the sampling tool's device passes (python -m txt2vid_amd.gan.sample) ------------------------------------------------
+ * t2v_clip_export: float clips to the frame cache's bytes. x: dense fp32 [B,C,T,H,W]; out: uint8 [B*T, C*H*W], one channel-planar
+ * row per frame, clip b's frames at rows b*T .. b*T+T-1 (the block layout t2v_clip_gather reads). The byte is
+ *   q = rint(x * 127.5f + 127.5f), the product and the sum two separately rounded fp32 operations (no fma), rint half to even,
+ *   clamped to [0, 255], NaN -> 0
+ * — the exact inverse of data.unit_range on its 256 values, and bit for bit numpy's float32 expression. 16-byte loads and dword
+ * stores where H*W % 4 == 0 and x / out are 16- / 4-byte aligned, one element per thread otherwise; a grid-stride loop keeps the
+ * grid at 2^20 blocks at most. One launch, no workspace. T2V_EINVAL, before any launch, on a NULL pointer, an extent < 1, H*W or
+ * B*C*T above 2^31 - 1. */
+int t2v_clip_export(const float* x, int B, int C, int T, int H, int W, uint8_t* out, void* stream);
+
+/* t2v_clip_nn: the nearest real clips of each sample in pixel space. g: dense fp32 [N, D] (the samples), r: dense fp32 [B, D] (one
+ * batch of real clips, the same flattening), both 16-byte aligned; 1 <= N, B <= T2V_CLIP_NN_MAX_ROWS, 1 <= K <= T2V_CLIP_NN_MAX_K,
+ * D % 4 == 0, 4 <= D <= 3*16*128*128, base >= 0. Per sample n the call merges the B candidates (d2(n, j), base + j) into the
+ * ascending list best_d2[n, 0..K) / best_idx[n, 0..K) (double / int64, dense [N, K]); the order is lexicographic on (distance,
+ * index): of two clips at the same distance the lower index comes first. The caller initialises the list to (+inf, -1); calls with
+ * consecutive bases stream a dataset through. A NaN distance never enters a list.
+ *   d2(n, j) = sum_k (g[n][k] - r[j][k])^2: the DIFFERENCE is formed in fp32, then fma(d, d, acc) — never |g|^2 + |r|^2 - 2 g.r.
+ * D is cut into ceil(D / t2v_clip_nn_chain(D)) slabs of t2v_clip_nn_chain(D) elements (the last one shorter): a slab's sum is ONE
+ * chain of fp32 fma's over its elements in ascending order (so the chain is also the slab length: 128 up to D = 65536, at most 512
+ * slabs beyond), the slabs' sums are added in fp64 in a fixed order. With u = 2^-24 and L the chain, |d2_hat - d2| <= ((1 + u)^(L+2)
+ * - 1) d2 (+ 2^-53 d2 per slab), d2 the exact sum over the same fp32 inputs: all terms are non-negative. Two launches,
+ * no atomics: the same bits run to run. ws holds t2v_clip_nn_ws_bytes(N, B, D) bytes (0 for sizes the entry point refuses), 4-byte
+ * aligned, uninitialised. Neither allocates or synchronises. T2V_EINVAL, before any launch, on anything else; t2v_clip_nn_chain
+ * returns T2V_EINVAL for a D the entry point refuses. */
+#define T2V_CLIP_NN_MAX_ROWS 64
+#define T2V_CLIP_NN_MAX_K 8
+int64_t t2v_clip_nn_ws_bytes(int N, int B, int64_t D);
+int t2v_clip_nn_chain(int64_t D);
+int t2v_clip_nn(const float* g, int N, const float* r, int B, int64_t D, int64_t base, int K, double* best_d2, int64_t* best_idx,
+                void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -293,11 +293,15 @@ SIGNATURES = {
     't2v_knn_radii_ws_bytes': [_I, _I, _I],
     't2v_prdc_counts': [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     't2v_prdc_counts_ws_bytes': [_I, _I, _I],
+    't2v_clip_export': [_P, _I, _I, _I, _I, _I, _P, _P],
+    't2v_clip_nn_ws_bytes': [_I, _I, _L],
+    't2v_clip_nn_chain': [_L],
+    't2v_clip_nn': [_P, _I, _P, _I, _L, _L, _I, _P, _P, _P, _P],
     't2v_prof_begin': [_I],
     't2v_prof_end': [C.POINTER(C.c_double), _I],
     't2v_version': [],
 }
-_RESTYPE = {'t2v_kid_sums_ws_bytes': C.c_size_t, 't2v_knn_radii_ws_bytes': C.c_size_t, 't2v_prdc_counts_ws_bytes': C.c_size_t, 't2v_multi_ws_floats': C.c_int64, 't2v_sn_ws_floats': C.c_int64, 't2v_pool_conv_fwd_ws_floats': C.c_int64, 't2v_pool_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_grouped_bias_slab_floats': C.c_int64, 't2v_conv_fwd_grouped_ws_floats': C.c_int64,
+_RESTYPE = {'t2v_clip_nn_ws_bytes': C.c_int64, 't2v_kid_sums_ws_bytes': C.c_size_t, 't2v_knn_radii_ws_bytes': C.c_size_t, 't2v_prdc_counts_ws_bytes': C.c_size_t, 't2v_multi_ws_floats': C.c_int64, 't2v_sn_ws_floats': C.c_int64, 't2v_pool_conv_fwd_ws_floats': C.c_int64, 't2v_pool_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_slab_floats': C.c_int64, 't2v_conv_wgrad_grouped_bias_slab_floats': C.c_int64, 't2v_conv_fwd_grouped_ws_floats': C.c_int64,
             't2v_conv_wgrad_grouped_slab_floats': C.c_int64, 't2v_conv_fwd_ws_floats': C.c_int64, 't2v_channel_sum_ws_floats': C.c_int64, 't2v_channel_sum_grouped_ws_floats': C.c_int64, 't2v_bn_ws_floats': C.c_int64, 't2v_cbn_ws_floats': C.c_int64, 't2v_version': C.c_char_p}
 
 _lib = None
