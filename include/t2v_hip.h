@@ -671,6 +671,18 @@ int t2v_synth_clips(const int64_t* index_dev, int B, int64_t seed, int T, int C,
 int t2v_clip_gather(const uint8_t* cache_u8, int64_t n_rows, const int64_t* row_index, int B, int T, int C, int H, int W,
                     const float* lut, float* out, int32_t* err_dev, void* stream);
 
+/* ---- input row, real data, augmented: the same gather through a per-clip window and direction -------------------------------
+ * For a frame-folder dataset with hflip / crop_jitter (not in the reference, whose flip at data/__init__.py:235-241
+ * is commented out): the cache stores frames of C*Hc*Wc bytes (the crop plus a margin on every side) and clip b reads the H x W
+ * window at (y0_b, x0_b) of each of its frames, mirrored left to right when flip_b is 1:
+ *   out[b,t,c,y,x] = lut[frame(row_index[b,t])[c, y0_b + y, x0_b + (flip_b ? W-1-x : x)]].
+ * win: int32 [B,4] on the device = (y0, x0, flip, 0) per clip; the other arguments as for t2v_clip_gather. Any C, Hc, Wc,
+ * H <= Hc, W <= Wc, any base alignment of cache_u8 and any x0; only bytes of the window are read (no widening of a row segment
+ * to aligned words), so nothing outside [cache_u8, cache_u8 + n_rows*C*Hc*Wc) is touched. A row index outside [0, n_rows), a
+ * window outside [0, Hc-H] x [0, Wc-W] or a flip outside {0, 1} is never used as given: it is clamped and err_dev is set to 1. */
+int t2v_clip_gather_aug(const uint8_t* cache_u8, int64_t n_rows, const int64_t* row_index, const int32_t* win, int B, int T, int C,
+                        int Hc, int Wc, int H, int W, const float* lut, float* out, int32_t* err_dev, void* stream);
+
 /* ---- optional launch instrumentation for bench.py's roofline line -----------------------------------
  * Between begin and end every conv-GEMM launch is bracketed by a hipEvent pair recorded on the launch
  * stream. end() synchronises and fills out[kind*3+{0,1,2}] = {total ms, executed flops, launches};

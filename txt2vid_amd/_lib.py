@@ -267,6 +267,7 @@ SIGNATURES = {
     't2v_pool_conv_plan': [_I, _P, _I, _I, _I, _I3],
     't2v_synth_clips': [_P, _I, _L, _I, _I, _I, _I3, _P, _P, _P, _P],
     't2v_clip_gather': [_P, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    't2v_clip_gather_aug': [_P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     't2v_tseed_fwd_bn': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P],
     't2v_tseed_fwd_tanh': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     't2v_tseed_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -181,6 +181,98 @@ __global__ __launch_bounds__(256) void clip_gather_k(const uint8_t* __restrict__
     for (int64_t e = lo; e < hi; ++e) dst[e] = s_lut[src[e]];
 }
 
+// clip_gather_k with a per-clip window and direction: out[b,t,c,y,x] = lut[frame(row)[c, y0 + y, x0 + (flip ? W-1-x : x)]], the
+// stored frame being C x Hc x Wc bytes. One workgroup row per output frame (blockIdx.x = slot, so row, window and every clamp are
+// uniform), one lane per 16 consecutive output floats, cut at 16-byte boundaries of the OUTPUT (a slot starts `mis` floats past
+// one when C*H*W is not a multiple of 4, so unit 0 and the last unit may be partial). The 16 source bytes of a unit lie in one
+// stored row whenever the unit does not cross an output row: they are read with one 16-byte load at whatever address they have
+// (no widening to aligned words, so no byte that is not needed is ever touched), reversed in registers for a flipped clip. A
+// unit that crosses an output row falls back to one 4-byte load per float4 that stays inside a row and to byte loads for the
+// rest. Full float4s are stored wide, partial ones (slot edges) and unaligned output buffers by scalars.
+struct AugPos { int c, y, x; };
+
+__device__ inline void aug_step(AugPos& p, int n, int H, int W) {
+    p.x += n;
+    while (p.x >= W) {
+        p.x -= W;
+        if (++p.y == H) { p.y = 0; ++p.c; }
+    }
+}
+
+__global__ __launch_bounds__(256) void clip_gather_aug_k(const uint8_t* __restrict__ cache, int64_t n_rows, const int64_t* __restrict__ row_index,
+                                                         const int32_t* __restrict__ win, int T, int C, int Hc, int Wc, int H, int W, int upr,
+                                                         const float* __restrict__ lut, float* __restrict__ out, int32_t* __restrict__ err) {
+    __shared__ float s_lut[256];
+    s_lut[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+    const int64_t slot = blockIdx.x;
+    const int N = C * H * W;
+    int64_t row = row_index[slot];
+    const int32_t* wb = win + (slot / T) * 4;
+    int y0 = wb[0], x0 = wb[1], flip = wb[2];
+    bool bad = false;
+    if (row < 0 || row >= n_rows) { row = row < 0 ? 0 : n_rows - 1; bad = true; }     // never dereferenced as given: clamped and flagged
+    if (y0 < 0 || y0 > Hc - H) { y0 = y0 < 0 ? 0 : Hc - H; bad = true; }
+    if (x0 < 0 || x0 > Wc - W) { x0 = x0 < 0 ? 0 : Wc - W; bad = true; }
+    if (flip < 0 || flip > 1) { flip = flip < 0 ? 0 : 1; bad = true; }
+    if (bad && err && threadIdx.x == 0 && blockIdx.y == 0) *err = 1;
+    const uint8_t* src = cache + row * ((int64_t)C * Hc * Wc) + (int64_t)y0 * Wc + x0;    // byte [c, y0, x0] of the frame, c = 0
+    const int64_t e0 = slot * N;                      // first output float of the slot
+    const int mis = (int)(e0 & 3);
+    float* dst = out + e0;
+    const bool wide = ((uintptr_t)out & 15u) == 0;
+    for (int k = blockIdx.y * 256 + threadIdx.x; k < upr; k += gridDim.y * 256) {
+        int i = 16 * k - mis;                         // first float of the unit inside the slot (< 0: the part in front belongs to slot - 1)
+        if (i >= N) break;
+        const int first = i < 0 ? 0 : i;
+        AugPos p;
+        p.c = first / (H * W);
+        const int r = first - p.c * (H * W);
+        p.y = r / W;
+        p.x = r - p.y * W;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};             // the unit's bytes in OUTPUT order, four per word
+        if (i >= 0 && i + 16 <= N && p.x + 16 <= W) {
+            const uint8_t* s = src + (p.c * Hc + p.y) * Wc + (flip ? W - 16 - p.x : p.x);
+            uint32_t t[4];
+            __builtin_memcpy(t, s, 16);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = flip ? __builtin_bswap32(t[3 - j]) : t[j];
+        } else {
+            int q = i;
+#pragma unroll
+            for (int j = 0; j < 4; ++j, q += 4) {
+                if (q >= 0 && q + 4 <= N && p.x + 4 <= W) {
+                    const uint8_t* s = src + (p.c * Hc + p.y) * Wc + (flip ? W - 4 - p.x : p.x);
+                    uint32_t t;
+                    __builtin_memcpy(&t, s, 4);
+                    w[j] = flip ? __builtin_bswap32(t) : t;
+                    aug_step(p, 4, H, W);
+                } else {
+                    for (int m = 0; m < 4; ++m) {
+                        if (q + m < 0 || q + m >= N) continue;
+                        w[j] |= (uint32_t)src[(p.c * Hc + p.y) * Wc + (flip ? W - 1 - p.x : p.x)] << (8 * m);
+                        aug_step(p, 1, H, W);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int q = i + 4 * j;
+            float v[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) v[m] = s_lut[(w[j] >> (8 * m)) & 0xffu];
+            if (wide && q >= 0 && q + 4 <= N) {
+                *reinterpret_cast<float4*>(dst + q) = make_float4(v[0], v[1], v[2], v[3]);
+            } else {
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    if (q + m >= 0 && q + m < N) dst[q + m] = v[m];
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int t2v_synth_clips(const int64_t* index_dev, int B, int64_t seed, int T, int C, int S, const int32_t* vocab_ids, float* vids,
@@ -205,5 +297,20 @@ extern "C" int t2v_clip_gather(const uint8_t* cache_u8, int64_t n_rows, const in
     (void)hipGetLastError();
     hipLaunchKernelGGL(clip_gather_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, cache_u8, n_rows, row_index, n_slots, N, upr,
                        lut, out, err_dev);
+    return hipGetLastError() == hipSuccess ? T2V_OK : T2V_ELAUNCH;
+}
+
+extern "C" int t2v_clip_gather_aug(const uint8_t* cache_u8, int64_t n_rows, const int64_t* row_index, const int32_t* win, int B, int T, int C,
+                                   int Hc, int Wc, int H, int W, const float* lut, float* out, int32_t* err_dev, void* stream) {
+    if (!cache_u8 || !row_index || !win || !lut || !out || n_rows < 1 || B < 1 || T < 1 || C < 1 || H < 1 || W < 1 || H > Hc || W > Wc)
+        return T2V_EINVAL;
+    const int64_t Nc = (int64_t)C * Hc * Wc, N = (int64_t)C * H * W, n_slots = (int64_t)B * T;
+    if (Nc >= (1LL << 30) || n_slots * N >= (1LL << 40) || n_rows >= (1LL << 40) / Nc || n_slots >= (1LL << 31)) return T2V_EINVAL;
+    if (((uintptr_t)out & 3u) != 0) return T2V_EINVAL;
+    const int upr = (int)(N / 16) + 2;                // units per slot: 16 floats each, cut at the output's 16-byte boundaries
+    const int by = (upr + 255) / 256;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(clip_gather_aug_k, dim3((unsigned)n_slots, (unsigned)(by < 65535 ? by : 65535)), dim3(256), 0, (hipStream_t)stream,
+                       cache_u8, n_rows, row_index, win, T, C, Hc, Wc, H, W, upr, lut, out, err_dev);
     return hipGetLastError() == hipSuccess ? T2V_OK : T2V_ELAUNCH;
 }

@@ -95,20 +95,27 @@ def unit_range(u8):
 def default_transform(frame_size=None, num_channels=3):
     """PIL image -> float32 [C,h,w] in [-1,1]: centre crop, (grey), /255, (x-0.5)/0.5 — the torchvision
     pipeline of data/__init__.py:357-370 without torchvision (absent here). The closure carries `crop` (h, w), `num_channels`
-    and `integer_part` (crop + convert, PIL -> PIL): what the HBM frame cache stores is that part's bytes."""
+    and `integer_part` (crop + convert, PIL -> PIL): what the HBM frame cache stores is that part's bytes. `integer_part(img, dy, dx,
+    margin)` displaces the crop box by (dy, dx) and enlarges it by `margin` on every side, and `transform(img, dy, dx, flip)` mirrors
+    the bytes left to right after crop and convert — the per-clip augmentation of `Dataset` (hflip / crop_jitter)."""
     fs = list(frame_size) if isinstance(frame_size, (list, tuple)) else [frame_size]
     if len(fs) == 1:
         fs.append(fs[0])
     ch, cw = int(fs[0]), int(fs[1])
 
-    def integer_part(img):
+    def integer_part(img, dy=0, dx=0, margin=0):
         w, h = img.size
+        # left / top are ALWAYS those of the plain crop: round() is half-to-even, so rounding an enlarged crop's offset instead
+        # would move the box by one pixel whenever (w - cw) and the margin are both odd
         left, top = int(round((w - cw) / 2.0)), int(round((h - ch) / 2.0))
-        img = img.crop((left, top, left + cw, top + ch))            # PIL zero-fills outside, like CenterCrop's pad
+        img = img.crop((left + dx - margin, top + dy - margin, left + dx + cw + margin, top + dy + ch + margin))   # PIL zero-fills outside, like CenterCrop's pad
         return img.convert('RGB' if num_channels == 3 else 'L')
 
-    def transform(img):
-        a = unit_range(integer_part(img))
+    def transform(img, dy=0, dx=0, flip=False):
+        a = np.asarray(integer_part(img, dy, dx), dtype=np.uint8)
+        if flip:
+            a = a[:, ::-1]                                          # the W axis of [h,w] / [h,w,3]
+        a = unit_range(a)
         a = a[None] if a.ndim == 2 else a.transpose(2, 0, 1)
         return torch.from_numpy(np.ascontiguousarray(a))
     transform.integer_part, transform.crop, transform.num_channels = integer_part, (ch, cw), int(num_channels)
@@ -118,16 +125,42 @@ def default_transform(frame_size=None, num_channels=3):
 class Dataset(torch.utils.data.Dataset):
     """Frame-folder reader with the contract of `txt2vid.data.Dataset` (:158-258), minus cv2 / DALI / lmdb:
     `captions` is a pickle {video id -> [sentence, ...]}; `video_dir/<id>/<n>.jpg|png` are the frames
-    (n integer, sorted numerically). One item per (video, sentence): (frames [T,C,h,w], token ids float)."""
+    (n integer, sorted numerically). One item per (video, sentence): (frames [T,C,h,w], token ids float).
+
+    Opt-in augmentation of the real clips (not in the reference), one draw per clip, the same for all its frames:
+    `hflip` mirrors the clip left to right with probability 1/2 (`hflip_swap=[[a, b], ...]` then exchanges the tokens of words a
+    and b in a flipped clip's caption); `crop_jitter=J` displaces `default_transform`'s crop box by (dy, dx), each uniform in
+    [-J, J]; `window=S` takes frames start + S*i of the sorted frame list, start uniform over the valid ones. The draws come from
+    global `np.random` in the order of `draw`; a key that is off draws nothing. `plain(idx)` is the item without any of them."""
 
     def __init__(self, video_dir=None, vocab=None, captions=None, transform=None, random_frames=0, num_frames=16,
-                 use_lmdb=False):
+                 use_lmdb=False, hflip=False, crop_jitter=0, window=0, hflip_swap=None):
         if use_lmdb:
             raise NotImplementedError('the caffe2-LMDB cache is not part of this build (no lmdb here)')
         import os
         from ..util.pick import load
         self.video_dir, self.vocab, self.transform = str(video_dir), vocab, transform
         self.random_frames, self.num_frames = int(random_frames or 0), num_frames
+        self.hflip, self.crop_jitter, self.window = bool(hflip), int(crop_jitter or 0), int(window or 0)
+        self.augmented = self.hflip or self.crop_jitter > 0 or self.window > 0
+        if self.crop_jitter < 0 or self.window < 0:
+            raise ValueError('crop_jitter=%d, window=%d: crop_jitter is a number of pixels >= 0, window a frame stride >= 1'
+                             % (self.crop_jitter, self.window))
+        if self.window and self.random_frames:
+            raise ValueError('window=%d and random_frames=%d both choose the frames of a clip: set one of them'
+                             % (self.window, self.random_frames))
+        if self.augmented and not all(hasattr(transform, a) for a in ('integer_part', 'crop', 'num_channels')):
+            raise ValueError('hflip / crop_jitter / window act on the crop of data.default_transform: a dataset with another '
+                             'transform (%r) cannot take them' % (transform,))
+        self.swap = {}
+        if hflip_swap:
+            if not self.hflip:
+                raise ValueError('hflip_swap names the words to exchange in a flipped clip\'s caption: it needs hflip')
+            for a, b in hflip_swap:
+                for w in (a, b):
+                    if str(w).lower() not in vocab.word2idx:
+                        raise ValueError('hflip_swap: the word %r is not in the vocabulary' % (w,))
+                self.swap[vocab(a)], self.swap[vocab(b)] = vocab(b), vocab(a)
         table = load(captions) if isinstance(captions, (str, os.PathLike)) else captions
         self.video_ids, self.captions, self.missing = [], [], 0
         for vid in table:
@@ -151,28 +184,79 @@ class Dataset(torch.utils.data.Dataset):
                 ext[int(stem)] = name
         return [(n, ext[n]) for n in sorted(ext)]
 
-    def tokens(self, idx):
-        """Token ids of item `idx`'s caption (<start> ... <end>)."""
+    def tokens(self, idx, flip=False):
+        """Token ids of item `idx`'s caption (<start> ... <end>); of a flipped clip, with the `hflip_swap` words exchanged."""
         toks = [self.vocab(t) for t in self.vocab.tokenize(self.captions[idx])]
         if toks[-1] != self.vocab(self.vocab.END):
             toks.append(self.vocab(self.vocab.END))
+        if flip and self.swap:
+            toks = [self.swap.get(t, t) for t in toks]
         return toks
 
-    def __getitem__(self, idx):
+    def span(self):
+        """Frames a `window` clip reaches over: (num_frames - 1) * window + 1."""
+        return (self.num_frames - 1) * self.window + 1
+
+    def check_span(self, video_id, count):
+        if count < self.span():
+            raise ValueError('video %s has %d frames, window=%d over %d frames needs at least %d'
+                             % (video_id, count, self.window, self.num_frames, self.span()))
+
+    def draw(self, video_id, count):
+        """The augmentation draws of one clip of a video with `count` frames, from global `np.random`, in the one order the host
+        items and `DeviceFrameLoader.plan` share: window start, then (dy, dx), then the flip; a key that is off draws nothing
+        (a `random_frames` pick, which `window` excludes, is drawn by the caller in the window start's place).
+        -> (start, dy, dx, flip)"""
+        start = dy = dx = flip = 0
+        if self.window:
+            self.check_span(video_id, count)
+            start = int(np.random.randint(0, count - self.span() + 1))
+        if self.crop_jitter:
+            dy, dx = (int(v) for v in np.random.randint(-self.crop_jitter, self.crop_jitter + 1, size=2))
+        if self.hflip:
+            flip = int(np.random.randint(0, 2))
+        return start, dy, dx, flip
+
+    def _frames(self, idx, picked, dy=0, dx=0, flip=0):
         import os
         from PIL import Image
         folder = os.path.join(self.video_dir, str(self.video_ids[idx]))
+        frames = []
+        for name in picked:
+            with Image.open(os.path.join(folder, name)) as img:
+                img.load()
+                if dy or dx or flip:
+                    frames.append(self.transform(img, dy=dy, dx=dx, flip=bool(flip)))
+                else:
+                    frames.append(self.transform(img) if self.transform else img)
+        return torch.stack(frames)
+
+    def __getitem__(self, idx):
         ext = dict(self.frame_files(self.video_ids[idx]))
         ids = sorted(ext)
-        n = self.random_frames if self.random_frames else self.num_frames
-        picked = pick_frames(ids, num_frames=n, random=bool(self.random_frames))
-        frames = []
-        for i in picked:
-            with Image.open(os.path.join(folder, ext[i])) as img:
-                img.load()
-                frames.append(self.transform(img) if self.transform else img)
-        frames = torch.stack(frames)
-        return frames, torch.tensor(self.tokens(idx), dtype=torch.float32)
+        if self.window:
+            start, dy, dx, flip = self.draw(self.video_ids[idx], len(ids))
+            picked = [ids[start + self.window * i] for i in range(self.num_frames)]
+        else:
+            n = self.random_frames if self.random_frames else self.num_frames
+            picked = pick_frames(ids, num_frames=n, random=bool(self.random_frames))
+            _, dy, dx, flip = self.draw(self.video_ids[idx], len(ids))
+        frames = self._frames(idx, [ext[i] for i in picked], dy, dx, flip)
+        return frames, torch.tensor(self.tokens(idx, flip), dtype=torch.float32)
+
+    def plain(self, idx):
+        """Item `idx` without augmentation and without a draw: centre crop, no flip, original caption; with `window` the centred
+        window, with `random_frames` the evenly strided pick of that many frames. What tools that read the data set by index
+        compare against (the nearest-clip search of gan/sample.py)."""
+        ext = dict(self.frame_files(self.video_ids[idx]))
+        ids = sorted(ext)
+        if self.window:
+            self.check_span(self.video_ids[idx], len(ids))
+            start = (len(ids) - self.span()) // 2
+            picked = [ids[start + self.window * i] for i in range(self.num_frames)]
+        else:
+            picked = pick_frames(ids, num_frames=self.random_frames or self.num_frames, random=False)
+        return self._frames(idx, [ext[i] for i in picked]), torch.tensor(self.tokens(idx), dtype=torch.float32)
 
 
 class SyntheticMovingDigits(torch.utils.data.Dataset):
@@ -295,12 +379,13 @@ def collate_fn(data):
 
 
 def my_dataset(data=None, vocab=None, anno=None, transform=None, random_frames=False, num_frames=16, use_lmdb=False,
-               on_device=False, cache_file=None, **synthetic_args):
+               on_device=False, cache_file=None, hflip=False, crop_jitter=0, window=0, hflip_swap=None, **synthetic_args):
     """Factory named by config/*.json (`"class": "txt2vid.data.my_dataset"`, data/__init__.py:376-377): a
     frame-folder `Dataset` when `data` is a directory (captions pickle = `--anno`); `data="synthetic"` (or a
     path that does not exist, e.g. the reference's own config/synth.json on a machine without the files)
     yields the synthetic clips, with `size= channels= length= seed=` forwarded. `on_device` (and, for a frame folder, `cache_file`)
-    is recorded on the dataset: `get_loader(..., device=cuda)` then serves the batches from HBM."""
+    is recorded on the dataset: `get_loader(..., device=cuda)` then serves the batches from HBM. `hflip`, `crop_jitter`, `window`
+    and `hflip_swap` augment a frame folder's clips (`Dataset`; both loaders, bit-identical); the synthetic clips refuse them."""
     import os
     if data is not None and data != 'synthetic' and os.path.isdir(str(data)):
         if anno is None:
@@ -308,9 +393,13 @@ def my_dataset(data=None, vocab=None, anno=None, transform=None, random_frames=F
         if transform is None:
             transform = default_transform([synthetic_args.get('size', 64)], synthetic_args.get('channels', 3))
         dset = Dataset(video_dir=data, vocab=vocab, captions=anno, transform=transform, random_frames=random_frames,
-                       num_frames=num_frames, use_lmdb=use_lmdb)
+                       num_frames=num_frames, use_lmdb=use_lmdb, hflip=hflip, crop_jitter=crop_jitter, window=window,
+                       hflip_swap=hflip_swap)
         dset.on_device, dset.cache_file = bool(on_device), cache_file
         return dset
+    if hflip or crop_jitter or window or hflip_swap:
+        raise ValueError('hflip / crop_jitter / window / hflip_swap augment a frame-folder dataset: the synthetic clips (data=%r) '
+                         'do not take them' % (data,))
     return SyntheticMovingDigits(num_frames=num_frames, vocab=vocab, on_device=on_device, **synthetic_args)
 
 
@@ -369,4 +458,4 @@ class DevicePrefetcher(object):
         return x, y
 
 
-from .frames import FrameCache, DeviceFrameLoader, clip_gather, frame_cache_for  # noqa: E402  (needs the names above)
+from .frames import FrameCache, DeviceFrameLoader, clip_gather, clip_gather_aug, frame_cache_for  # noqa: E402  (needs the names above)

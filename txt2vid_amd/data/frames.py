@@ -5,6 +5,10 @@ the caption tokens cross PCIe; no JPEG is decoded, no float is made and no pixel
 What is cached is the INTEGER part of `default_transform` (centre crop with zero fill, `convert('RGB' | 'L')`, done by PIL exactly
 as the host path does it); the float part is a 256-entry table computed with the host path's own numpy expression (`unit_range`),
 so `lut[cache]` equals the host item bit for bit whatever the device's arithmetic does.
+
+A dataset that augments its clips (`hflip`, `crop_jitter`, `window`) is served from the same cache by a different read
+pattern: the crop is stored with a margin, `plan` makes the host items' draws, and `t2v_clip_gather_aug` reads each clip's window,
+mirrored where drawn.
 """
 import json
 import os
@@ -27,14 +31,17 @@ class FrameCache(object):
     """uint8 frames of a frame-folder `Dataset`, channel-planar, one row [C,h,w] per frame, all videos back to back:
     `block` [rows, C*h*w] uint8 (host; `to(device)` uploads it), `table` {video id -> (first row, row count)}. With
     `random_frames == 0` only the strided pick of every video is stored (its `num_frames` rows, in pick order); otherwise every
-    frame, so that any random pick is a set of rows. Items that share a video (several captions) share its rows."""
+    frame, so that any random pick is a set of rows. Items that share a video (several captions) share its rows. A dataset with
+    `crop_jitter=J` stores the crop enlarged by a margin of J pixels on every side (`stored` = (h + 2J, w + 2J), `crop` stays the
+    output crop): a jittered crop is then a window of the stored frame; a `window` dataset stores every frame."""
 
     RESERVE_BYTES = 16 << 30          # HBM left to the training step when `to()` sizes the cache against the free memory
 
     def __init__(self, block, table, meta):
         self.block, self.table, self.meta = block, table, meta
-        self.crop, self.channels = tuple(meta['crop']), int(meta['channels'])
-        self.row_bytes = self.channels * self.crop[0] * self.crop[1]
+        self.crop, self.channels, self.margin = tuple(meta['crop']), int(meta['channels']), int(meta.get('margin', 0))
+        self.stored = (self.crop[0] + 2 * self.margin, self.crop[1] + 2 * self.margin)
+        self.row_bytes = self.channels * self.stored[0] * self.stored[1]
         self.lut = np.ascontiguousarray(unit_range(np.arange(256, dtype=np.uint8)))       # lut[u] == what the host transform makes of byte u
         self.device_block = self.device_lut = None
         self.seconds, self.source = 0.0, 'built'
@@ -63,8 +70,11 @@ class FrameCache(object):
             if str(vid) not in listing:
                 folder = os.path.join(dset.video_dir, str(vid))
                 listing[str(vid)] = [[name, os.path.getsize(os.path.join(folder, name))] for _, name in dset.frame_files(vid)]
-        return {'version': CACHE_VERSION, 'crop': list(crop), 'channels': ch, 'all_frames': bool(dset.random_frames),
-                'num_frames': int(dset.num_frames), 'listing': listing}
+        meta = {'version': CACHE_VERSION, 'crop': list(crop), 'channels': ch,
+                'all_frames': bool(dset.random_frames or getattr(dset, 'window', 0)), 'num_frames': int(dset.num_frames), 'listing': listing}
+        if getattr(dset, 'crop_jitter', 0):
+            meta['margin'] = int(dset.crop_jitter)          # (absent without jitter: such sidecars are what they always were)
+        return meta
 
     @classmethod
     def build(cls, dset):
@@ -72,21 +82,24 @@ class FrameCache(object):
         t0 = time.time()
         part, crop, ch = cls._spec(dset)
         meta = cls._meta(dset)
+        margin = int(meta.get('margin', 0))
         table, chosen, first = {}, [], 0
         for vid, files in meta['listing'].items():
             names = [f[0] for f in files]
-            if not dset.random_frames:
+            if getattr(dset, 'window', 0):
+                dset.check_span(vid, len(names))
+            elif not dset.random_frames:
                 names = pick_frames(names, num_frames=dset.num_frames, random=False)
             elif len(names) < dset.random_frames:
                 raise ValueError('video %s has %d frames, random_frames=%d needs at least that many' % (vid, len(names), dset.random_frames))
             table[vid] = (first, len(names))
             chosen.extend((vid, n) for n in names)
             first += len(names)
-        block = np.empty((first, ch * crop[0] * crop[1]), dtype=np.uint8)
+        block = np.empty((first, ch * (crop[0] + 2 * margin) * (crop[1] + 2 * margin)), dtype=np.uint8)
         for r, (vid, name) in enumerate(chosen):
             with Image.open(os.path.join(dset.video_dir, vid, name)) as img:
                 img.load()
-                a = np.asarray(part(img), dtype=np.uint8)
+                a = np.asarray(part(img, margin=margin) if margin else part(img), dtype=np.uint8)
             block[r] = (a[None] if a.ndim == 2 else a.transpose(2, 0, 1)).reshape(-1)
         meta['table'] = {vid: list(fc) for vid, fc in table.items()}
         cache = cls(block, table, meta)
@@ -104,7 +117,8 @@ class FrameCache(object):
     @classmethod
     def load(cls, path, dset):
         """The cache written by `save`, memory-mapped; refused (ValueError) unless its sidecar matches `dset`: same crop, channels,
-        frame selection and folder listing (names and sizes of every frame file of every video the dataset serves)."""
+        frame selection and folder listing (names and sizes of every frame file of every video the dataset serves), and a margin
+        (absent = 0) at least the dataset's `crop_jitter` — a larger one serves too, the windows then start further in."""
         t0 = time.time()
         npy, side = _paths(path)
         with open(side) as f:
@@ -119,10 +133,15 @@ class FrameCache(object):
                     a, b = '%d videos' % len(a or {}), '%d videos (or other frame files)' % len(b)
                 raise ValueError('frame cache %s was not built for this dataset: its %s is %s, the dataset needs %s — rebuild it '
                                  '(python -m txt2vid_amd.data.cache)' % (npy, key, a, b))
+        margin = int(meta.get('margin', 0))
+        if margin < int(want.get('margin', 0)):
+            raise ValueError('frame cache %s was not built for this dataset: its margin is %s, the dataset needs %s — rebuild it '
+                             '(python -m txt2vid_amd.data.cache)' % (npy, margin, want['margin']))
         block = np.load(npy, mmap_mode='r')
         table = {vid: (int(fc[0]), int(fc[1])) for vid, fc in meta['table'].items()}
         rows = sum(c for _, c in table.values())
-        if block.dtype != np.uint8 or block.ndim != 2 or block.shape != (rows, meta['channels'] * meta['crop'][0] * meta['crop'][1]):
+        stored = meta['channels'] * (meta['crop'][0] + 2 * margin) * (meta['crop'][1] + 2 * margin)
+        if block.dtype != np.uint8 or block.ndim != 2 or block.shape != (rows, stored):
             raise ValueError('frame cache %s: the block %s %s does not match its sidecar (%d rows)' % (npy, block.dtype, block.shape, rows))
         cache = cls(block, table, meta)
         cache.seconds, cache.source = time.time() - t0, 'loaded from %s' % npy
@@ -194,6 +213,36 @@ def clip_gather(cache_u8, rows, lut, shape, err, out=None):
     return out
 
 
+def clip_gather_aug(cache_u8, rows, win, lut, shape, stored, err, out=None):
+    """out[b,t,c,y,x] = lut[frame(rows[b,t])[c, y0_b + y, x0_b + (flip_b ? W-1-x : x)]] (`t2v_clip_gather_aug`): `clip_gather`
+    through a per-clip window of the stored frames. cache_u8 uint8 [n_rows * C*Hc*Wc], rows int64 [B*T], win int32 [B,4] =
+    (y0, x0, flip, 0), lut float32 [256], all on the device; shape (B,T,C,H,W), stored (Hc, Wc); err int32 [1] (set to 1 when a
+    row index, a window origin or a flip had to be clamped)."""
+    import ctypes as C
+    from .._lib import lib, check
+    from .._ops import _stream
+    B, T, Cc, H, W = [int(v) for v in shape]
+    Hc, Wc = int(stored[0]), int(stored[1])
+    n = Cc * Hc * Wc
+    for t, dt, numel in ((cache_u8, torch.uint8, None), (rows, torch.int64, B * T), (win, torch.int32, B * 4), (lut, torch.float32, 256),
+                         (err, torch.int32, 1)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+            raise RuntimeError('clip_gather_aug: dense device tensors uint8 / int64 [B*T] / int32 [B,4] / float32 [256] / int32 [1] '
+                               'expected (the HIP path has no CPU fallback)')
+    if H > Hc or W > Wc:
+        raise ValueError('clip_gather_aug: a %dx%d window does not fit the stored %dx%d frames' % (H, W, Hc, Wc))
+    if cache_u8.numel() < n or cache_u8.numel() % n:
+        raise ValueError('clip_gather_aug: the cache holds %d bytes, not a whole number of %d-byte frames' % (cache_u8.numel(), n))
+    if out is None:
+        out = torch.empty((B, T, Cc, H, W), device=cache_u8.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, T, Cc, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError('clip_gather_aug: the output buffer must be dense [B,T,C,H,W] float32 on the device')
+    check(lib().t2v_clip_gather_aug(C.c_void_p(cache_u8.data_ptr()), cache_u8.numel() // n, C.c_void_p(rows.data_ptr()),
+                                    C.c_void_p(win.data_ptr()), B, T, Cc, Hc, Wc, H, W, C.c_void_p(lut.data_ptr()),
+                                    C.c_void_p(out.data_ptr()), C.c_void_p(err.data_ptr()), _stream()), 't2v_clip_gather_aug')
+    return out
+
+
 class DeviceFrameLoader(object):
     """Stands in for `DataLoader(Dataset, collate_fn=collate_fn, num_workers=0)` when the frames live in HBM: same protocol as
     `DeviceSyntheticLoader` (len, iter -> (videos [B,T,C,h,w] float32 on the device, tokens [B,L] int64, lengths), drop_last) and
@@ -209,7 +258,7 @@ class DeviceFrameLoader(object):
         self._ring, self._pos, self._err = [], 0, None
         from ..util.log import status
         status('frame cache %s in %.2f s: %d frames of %dx%dx%d uint8, %.1f MB on %s; batches are gathered on the device (--workers is '
-               'not used on this path)' % (cache.source, cache.seconds, cache.block.shape[0], cache.channels, cache.crop[0], cache.crop[1],
+               'not used on this path)' % (cache.source, cache.seconds, cache.block.shape[0], cache.channels, cache.stored[0], cache.stored[1],
                                            cache.nbytes / 1e6, self.device))
 
     def __len__(self):
@@ -224,40 +273,64 @@ class DeviceFrameLoader(object):
 
     def plan(self, indices):
         """Host half of a batch (no pixels): for the items in sampler order draw the frame pick and tokenise, then apply `collate_fn`'s
-        rule (stable sort by caption length, descending; zero-padded int64 tokens). -> (rows int64 [B,T], tokens [B,L], lengths)."""
-        ds, picked, toks = self.dataset, [], []
+        rule (stable sort by caption length, descending; zero-padded int64 tokens). -> (rows int64 [B,T], tokens [B,L], lengths);
+        for a dataset that flips or jitters (or a cache with a margin), a fourth element: win int32 [B,4] = (y0, x0, flip, 0) per
+        clip, sorted with the rows, the window `t2v_clip_gather_aug` reads. The augmentation draws are `Dataset.draw`'s, item by
+        item, as the host items make them; `window` alone only changes rows."""
+        ds, picked, toks, wins = self.dataset, [], [], []
+        aug, margin = getattr(ds, 'augmented', False), self.cache.margin
         for i in indices:
             first, count = self.cache.rows_of(ds.video_ids[int(i)])
-            if ds.random_frames:
+            if not aug:                                    # the keys are off: what this loop always did
+                if ds.random_frames:
+                    picked.append(pick_frames(range(first, first + count), num_frames=ds.random_frames, random=True))
+                else:
+                    picked.append(list(range(first, first + count)))
+                toks.append(ds.tokens(int(i)))
+                continue
+            if ds.random_frames:                           # (drawn in the window start's place, as the host item does)
                 picked.append(pick_frames(range(first, first + count), num_frames=ds.random_frames, random=True))
-            else:
+            start, dy, dx, flip = ds.draw(ds.video_ids[int(i)], count)
+            if ds.window:
+                picked.append([first + start + ds.window * t for t in range(ds.num_frames)])
+            elif not ds.random_frames:
                 picked.append(list(range(first, first + count)))
-            toks.append(ds.tokens(int(i)))
+            wins.append([margin + dy, margin + dx, flip, 0])
+            toks.append(ds.tokens(int(i), flip))
         order = sorted(range(len(toks)), key=lambda k: len(toks[k]), reverse=True)
         lengths = [len(toks[k]) for k in order]
         rows = torch.tensor([picked[k] for k in order], dtype=torch.int64)
         tokens = torch.zeros(len(order), max(lengths), dtype=torch.long)
         for j, k in enumerate(order):
             tokens[j, :lengths[j]] = torch.tensor(toks[k], dtype=torch.long)
-        return rows, tokens, lengths
+        if not (margin or (aug and (ds.hflip or ds.crop_jitter))):
+            return rows, tokens, lengths
+        win = torch.tensor([wins[k] for k in order] if aug else [[margin, margin, 0, 0]] * len(order), dtype=torch.int32)
+        return rows, tokens, lengths, win
 
-    def _upload(self, rows, tokens):
-        """rows and tokens through one pinned slot of a small ring and one non-blocking copy: the host never waits for the stream
-        (a slot is reused only after the copy that read it has finished — an event per slot, normally long past)."""
+    def _upload(self, rows, tokens, win=None):
+        """rows, tokens (and the windows, two int32 pairs per int64 pair) through one pinned slot of a small ring and one
+        non-blocking copy: the host never waits for the stream (a slot is reused only after the copy that read it has finished — an
+        event per slot, normally long past)."""
         n_r, n_t = rows.numel(), tokens.numel()
+        n_w = 0 if win is None else win.numel() // 2
         if not self._ring:
             self._ring = [[None, torch.cuda.Event()] for _ in range(self.RING)]
         slot = self._ring[self._pos % self.RING]
         self._pos += 1
-        if slot[0] is None or slot[0].numel() < n_r + n_t:
-            slot[0] = torch.empty((2 * (n_r + n_t),), dtype=torch.int64).pin_memory()
+        if slot[0] is None or slot[0].numel() < n_r + n_t + n_w:
+            slot[0] = torch.empty((2 * (n_r + n_t + n_w),), dtype=torch.int64).pin_memory()
         else:
             slot[1].synchronize()
         slot[0][:n_r].copy_(rows.reshape(-1))
         slot[0][n_r:n_r + n_t].copy_(tokens.reshape(-1))
-        dev = torch.empty((n_r + n_t,), dtype=torch.int64, device=self.device)
-        dev.copy_(slot[0][:n_r + n_t], non_blocking=True)
+        if n_w:
+            slot[0][n_r + n_t:n_r + n_t + n_w].copy_(win.reshape(-1).view(torch.int64))
+        dev = torch.empty((n_r + n_t + n_w,), dtype=torch.int64, device=self.device)
+        dev.copy_(slot[0][:n_r + n_t + n_w], non_blocking=True)
         slot[1].record()
+        if n_w:
+            return dev[:n_r], dev[n_r:n_r + n_t].view(tokens.shape), dev[n_r + n_t:].view(torch.int32).view(win.shape)
         return dev[:n_r], dev[n_r:].view(tokens.shape)
 
     def device_batch(self, indices):
@@ -267,19 +340,24 @@ class DeviceFrameLoader(object):
             self.cache.to(self.device, max_bytes=self.max_bytes)
         if self._err is None:
             self._err = torch.zeros((1,), dtype=torch.int32).to(self.device)            # (zero by copy: no fill kernel)
-        rows, tokens, lengths = self.plan(indices)
-        rows_dev, tokens_dev = self._upload(rows, tokens)
+        rows, tokens, lengths, *win = self.plan(indices)
         B, T = rows.shape
-        vids = clip_gather(self.cache.device_block, rows_dev, self.cache.device_lut,
-                           (B, T, self.cache.channels, self.cache.crop[0], self.cache.crop[1]), self._err)
+        shape = (B, T, self.cache.channels, self.cache.crop[0], self.cache.crop[1])
+        if win:                                                       # flip, jitter or a cache with a margin: the windowed gather
+            rows_dev, tokens_dev, win_dev = self._upload(rows, tokens, win[0])
+            vids = clip_gather_aug(self.cache.device_block, rows_dev, win_dev, self.cache.device_lut, shape, self.cache.stored, self._err)
+        else:
+            rows_dev, tokens_dev = self._upload(rows, tokens)
+            vids = clip_gather(self.cache.device_block, rows_dev, self.cache.device_lut, shape, self._err)
         return vids, tokens_dev, lengths
 
     def check_rows(self):
-        """Raise if the gather kernel had to clamp a row index since the last check (device flag; one 4-byte read-back)."""
+        """Raise if a gather kernel had to clamp a row index (or the augmented one a window or a flip) since the last check
+        (device flag; one 4-byte read-back)."""
         if self._err is not None and int(self._err.item()) != 0:
             self._err.zero_()
-            raise RuntimeError('t2v_clip_gather: a row index lay outside the frame cache (device flag set): the batch was built from '
-                               'clamped rows and is not what the host loader would have produced')
+            raise RuntimeError('t2v_clip_gather: a row index (or, augmented, a window) lay outside the frame cache (device flag set): '
+                               'the batch was built from clamped values and is not what the host loader would have produced')
 
     def __iter__(self):
         order = self.epoch_order()

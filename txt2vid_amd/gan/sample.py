@@ -283,8 +283,10 @@ def forked_host():
 
 
 def _real_batch(dset, lo, hi, device):
-    """Items lo..hi-1 by index, stacked and uploaded: [b, C, T, H, W] dense."""
-    x = torch.stack([dset[i][0] for i in range(lo, hi)]).to(device)
+    """Items lo..hi-1 by index, stacked and uploaded: [b, C, T, H, W] dense. Of a data set that augments its clips, the plain items
+    (`Dataset.plain`: no flip, no jitter, the centred window, no draw): the search compares against the clips as they are."""
+    item = dset.plain if getattr(dset, 'augmented', False) else dset.__getitem__
+    x = torch.stack([item(i)[0] for i in range(lo, hi)]).to(device)
     return TF.video_to_channel_first(x)
 
 
