@@ -784,6 +784,39 @@ int t2v_diffaug_gated_fwd(const t2v_aug_member* members, const float* const* gat
 int t2v_diffaug_gated_bwd(const t2v_aug_member* members, const float* const* gates, int n, const float* p, void* stream);
 int t2v_ada_update(float* ada, const t2v_ada_level* levels, int n, float target, float step, int interval, void* stream);
 
+/* ---- geometric augmentation of the discriminator's inputs (ADA's x-flip, isotropic scaling, rotation; opt-in through the names
+ * flip, scale, rotate of --D_aug; not in the reference) -----------------------------------------------------------
+ * ONE bilinear resampling per clip [C, T, S, S], constant over its frames and channels, run in front of the colour /
+ * translation / cutout launch. The definition is the one in txt2vid_amd/functional_aug.py (`geo_params`). Members are
+ * t2v_aug_member as above with `u` pointing at the block v [rows, T2V_AUG_K] of uniforms in [0, 1) (clip j reads row
+ * j * row_stride) and `policy` a non-empty subset of T2V_AUG_FLIP | T2V_AUG_SCALE | T2V_AUG_ROTATE:
+ *   column 0  flip:    f = -1 (mirror left <-> right) iff v0 < 0.5, else +1
+ *   column 1  scale:   s = exp2((2 v1 - 1) * 0.4)
+ *   column 2  rotate:  theta = (2 v2 - 1) * pi / 6                                      columns 3-7 unused
+ * A transformation outside the (effective) policy takes f = +1, s = 1, theta = 0. The sampling matrix
+ *   m00 = f cos(theta) / s,  m01 = f sin(theta) / s,  m10 = -sin(theta) / s,  m11 = cos(theta) / s
+ * is formed in double from the fp32 draw and rounded once to fp32; everything per pixel is fp32. With half = S / 2, output pixel
+ * (h, w) has xo = (w + 0.5) - half, yo = (h + 0.5) - half and samples the input at
+ *   px = ((m00 xo + m01 yo) + half) - 0.5,   py = ((m10 xo + m11 yo) + half) - 0.5,
+ * x0 = floor(px), wx = px - x0 (the same for y): the bilinear blend of the taps (y0 + dy, x0 + dx), dy, dx in {0, 1}, with the
+ * weights (dy ? wy : 1 - wy) * (dx ? wx : 1 - wx), summed in the order (0,0), (0,1), (1,0), (1,1); a tap outside the frame
+ * contributes zero. Identity parameters reproduce the input, a pure flip is an exact mirror (px = S - 1 - w).
+ * t2v_geoaug_fwd: y = R(x). t2v_geoaug_bwd: x holds dL/dy, y receives dL/dx = R^T(dL/dy) as a GATHER: input pixel i sums, in
+ * row-major order over the 5 x 5 output pixels around the pre-image of i (the only ones whose taps can reach i, because
+ * s (|cos| + |sin|) < 1.81), weight(o, i) * dL/dy[o], the weight computed by the device function of the forward: the exact
+ * transpose weight by weight, the same bits run to run, no atomics.
+ * Gating: gates == NULL && p == NULL is the ungated form; otherwise both are given, `gates` is a HOST array of n
+ * device pointers (gates[i] == NULL leaves member i ungated), clip j of member i reads row j * row_stride of gates[i]
+ * [rows, T2V_AUG_K] and p[0] from DEVICE memory when the launch runs, and its
+ *   effective policy = policy & (8 [g3 < p] | 16 [g4 < p] | 32 [g5 < p]),   a strict fp32 <.
+ * A clip whose effective policy is 0 is copied, forward and adjoint. fp32, x != y. Plain loads and stores; neither allocates nor
+ * synchronises; both can be captured. T2V_EINVAL, before any launch, on n outside 1..T2V_MAX_GROUPS, null pointers, empty extents,
+ * a policy without a geometric bit or with any other bit, row_stride < 1, a parameter block with fewer than
+ * (N - 1) * row_stride + 1 rows, or exactly one of gates / p given. */
+enum { T2V_AUG_FLIP = 8, T2V_AUG_SCALE = 16, T2V_AUG_ROTATE = 32 };
+int t2v_geoaug_fwd(const t2v_aug_member* members, const float* const* gates, int n, const float* p, void* stream);
+int t2v_geoaug_bwd(const t2v_aug_member* members, const float* const* gates, int n, const float* p, void* stream);
+
 /* ---- LeCam regularisation of the discriminator (Tseng et al. 2021; opt-in, --D_lecam) -------------------------------
  * lecam float32[20] (device) = { n, R_last, gate_last, L, alpha_R[0..7], alpha_F[0..7] }: n counts the D steps seen (exact up to
  * 2^24), the anchors alpha_R[l] / alpha_F[l] are moving averages of the unconditional logits of level l on real / generated clips.

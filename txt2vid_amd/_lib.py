@@ -278,6 +278,8 @@ SIGNATURES = {
     't2v_diffaug_gated_fwd': [_P, _P, _I, _P, _P],
     't2v_diffaug_gated_bwd': [_P, _P, _I, _P, _P],
     't2v_ada_update': [_P, _P, _I, _F, _F, _I, _P],
+    't2v_geoaug_fwd': [_P, _P, _I, _P, _P],
+    't2v_geoaug_bwd': [_P, _P, _I, _P, _P],
     't2v_lecam_fwd': [_P, _P, _I, _F, _I, _P, _P, _P],
     't2v_lecam_bwd': [_P, _I, _P, _P, _P],
     't2v_proj_rows': [_P, _I, _P, _I, _I, _P],

@@ -40,13 +40,19 @@ class HostDraws(object):
         """eps ~ N(0, 1) [b, d] of the generator's conditioning augmentation (one draw per generator forward, like z)."""
         return torch.randn(b, d).to(device, non_blocking=True)
 
-    def aug(self, b, device, gated=False):
+    def aug(self, b, device, gated=False, geo=False):
         """One block u [b, AUG_K] of uniforms for an augmentation of D's inputs (functional_aug), drawn when it is consumed.
-        `gated` (adaptive strength): (u, g), the gate block g [b, AUG_K] drawn immediately after u."""
+        `gated` (adaptive strength): (u, g), the gate block g [b, AUG_K] drawn immediately after u. `geo` (a policy
+        with a geometric name): one more block v [b, AUG_K] drawn behind them, (u, v) or (u, g, v)."""
         u = torch.rand(b, AUG_K).to(device, non_blocking=True)
-        if not gated:
+        if not gated and not geo:
             return u
-        return u, torch.rand(b, AUG_K).to(device, non_blocking=True)
+        out = (u,)
+        if gated:
+            out += (torch.rand(b, AUG_K).to(device, non_blocking=True),)
+        if geo:
+            out += (torch.rand(b, AUG_K).to(device, non_blocking=True),)
+        return out
 
     def perm(self, n, device):
         """A non-identity permutation of range(n) from numpy's global RNG (util/misc.gen_perm), as a device int32 tensor."""
@@ -57,7 +63,7 @@ class HostDraws(object):
 
 class StaticDraws(object):
     def __init__(self, device, batch, latent, n_levels, n_gen_phases=3, gp=True, subsample_input=True, n_perms=0,
-                 n_d_steps=1, n_g_steps=1, ca_dim=0, n_aug=0):
+                 n_d_steps=1, n_g_steps=1, ca_dim=0, n_aug=0, n_geo=0):
         self.n_perms = n_perms                      # caption permutations per iteration (conditional path: D steps, real_pred)
         self.n_d_steps, self.n_g_steps = n_d_steps, n_g_steps     # one set of GP alphas per D step, of G phases per G forward
         self._p = 0
@@ -70,9 +76,14 @@ class StaticDraws(object):
         if n_aug not in (0, 2 * n_d_steps + n_g_steps + 1, 2 * (2 * n_d_steps + n_g_steps + 1)):
             raise ValueError('an iteration of %d D and %d G steps consumes %d augmentation blocks (twice as many with gates), not %d'
                              % (n_d_steps, n_g_steps, 2 * n_d_steps + n_g_steps + 1, n_aug))
-        self.n_aug = n_aug
+        # a policy with a geometric name: one more block v behind every u (and its g), 2N + M + 1 of them (0: none)
+        if n_geo not in (0, 2 * n_d_steps + n_g_steps + 1) or (n_geo and not n_aug):
+            raise ValueError('an iteration of %d D and %d G steps consumes %d geometric blocks, each behind an augmentation block, '
+                             'not %d' % (n_d_steps, n_g_steps, 2 * n_d_steps + n_g_steps + 1, n_geo))
+        self.n_aug, self.n_geo = n_aug, n_geo
         self.gated = n_aug > 2 * n_d_steps + n_g_steps + 1
-        self._w = 2 if self.gated else 1            # blocks per draw: u alone, or u and its gate block g right behind it
+        self.geo = n_geo > 0
+        self._w = 1 + int(self.gated) + int(self.geo)     # blocks per draw: u, its gate block g, its geometric block v, in a row
         self.bs = [batch]
         for _ in range(n_levels - 1):
             self.bs.append((self.bs[-1] + 1) // 2)
@@ -82,7 +93,7 @@ class StaticDraws(object):
         # copy node per replayed iteration instead of four (a copy node costs ~20 us of idle time in the replayed graph)
         n_int, n_z, n_a, n_p = n_levels + n_gen_phases * n_g_steps, batch * latent, sum(self.bs) * n_d_steps, max(1, n_perms) * batch
         n_e = batch * ca_dim * n_g_steps
-        n_u = batch * AUG_K * n_aug
+        n_u = batch * AUG_K * (n_aug + n_geo)
         # The staging side is a RING of pinned buffers: the upload is asynchronous and the training loop runs the host ahead of
         # the GPU (losses are read one iteration late), so a single staging buffer would be rewritten with iteration i + 1's draws
         # before the copy of iteration i has executed. A slot is reused only after the event behind its last copy has completed.
@@ -104,7 +115,7 @@ class StaticDraws(object):
             p_ = buf[o:o + n_p].view(max(1, n_perms), batch); o += n_p
             e_ = buf[o:o + n_e].view(torch.float32).view(n_g_steps, batch, ca_dim) if n_e else None
             o += n_e
-            u_ = buf[o:o + n_u].view(torch.float32).view(n_aug, batch, AUG_K) if n_u else None
+            u_ = buf[o:o + n_u].view(torch.float32).view(n_aug + n_geo, batch, AUG_K) if n_u else None
             return i_, z_, a_, p_, e_, u_
         self._carve = carve
         self.h_int, self.h_z, self.h_a, self.h_perm, self.h_eps, self.h_u = carve(self.h_all)
@@ -119,7 +130,8 @@ class StaticDraws(object):
         alphas, then eps j, phases j for each later forward j. With augmentation of D's inputs every D step draws a real and a
         generated block in front of its alphas, G part 0 draws a real and a generated block behind the last D step, and every later
         G forward j draws a generated block behind its phases. With gated augmentation every one of these blocks u is followed at
-        once by its gate block g (u, g, u, g, ...), next to it in the staging buffer."""
+        once by its gate block g (u, g, u, g, ...), next to it in the staging buffer. With a geometric policy every one of them is
+        followed, behind its gate block if it has one, by its geometric block v (u, [g], v, u, [g], v, ...), in the same buffer."""
         slot = self._slot
         self._slot = (slot + 1) % self.RING
         if self.h_events[slot] is not None:
@@ -207,11 +219,11 @@ class StaticDraws(object):
         self._e += 1
         return self.d_eps[k]
 
-    def aug(self, b, device, gated=False):
-        assert b == self.batch and self._u < self.n_aug and bool(gated) == self.gated
+    def aug(self, b, device, gated=False, geo=False):
+        assert b == self.batch and self._u < self.n_aug + self.n_geo and bool(gated) == self.gated and bool(geo) == self.geo
         k = self._u
         self._u += self._w
-        return (self.d_u[k], self.d_u[k + 1]) if self.gated else self.d_u[k]
+        return tuple(self.d_u[k + i] for i in range(self._w)) if self._w > 1 else self.d_u[k]
 
     def rewind(self):
         self._i = self._a = self._p = self._e = self._u = 0

@@ -11,7 +11,9 @@ gen_perm (numpy), 4x GP alpha (losses.py:140-145), gen_perm for real_pred (train
 gen_perm for real_pred, then 3x Subsample per later G forward (DESIGN "D:G step schedule"). With --D_aug every D step
 draws a real and a generated augmentation block in front of its alphas, G part 0 a real and a generated block, every later G
 step a generated block behind its forward's draws. With gated augmentation (--D_aug_p < 1 or --D_ada) every such
-block is followed at once by its gate block.
+block is followed at once by its gate block. With a geometric name in the policy (flip, scale, rotate) every such
+block is followed, behind its gate block if there is one, by its geometric block: u_real, [g_real], v_real, u_fake, [g_fake],
+v_fake at a site with both lists.
 """
 import argparse
 import os
@@ -96,7 +98,11 @@ def add_params_to_parser(parser):
                         help='(new) the average copies the weights for the first N generator updates')
     parser.add_argument('--D_aug', type=_aug_policy, default='',
                         help='(new) differentiable augmentation of every clip the discriminator sees: a comma-separated subset of '
-                             'color,translation,cutout (applied in that order); empty = off')
+                             'color,translation,cutout,flip,scale,rotate; empty = off. flip, scale and rotate (x-flip with '
+                             'probability 1/2, isotropic scaling by 2^(+-0.4), rotation by +-30 degrees) are one bilinear '
+                             'resampling per clip, applied first; then color, translation, cutout in that order. The scaling and '
+                             'rotation ranges follow the ADA paper\'s values for images: nobody has tuned them for video. Leave '
+                             'flip out when captions name a side or a direction')
     parser.add_argument('--D_aug_p', type=_probability, default=None,
                         help='(new) apply each transformation of --D_aug per clip with this probability, in [0, 1]: the fixed '
                              'strength, or the initial one under --D_ada. Default 1.0 without --D_ada (every clip, as --D_aug '
@@ -213,8 +219,9 @@ class TrainStep(object):
         # differentiable augmentation of D's inputs (--D_aug, not in the reference; functional_aug): every list of clips handed to
         # discrim_step / gen_step / gen_step_fused / the real_pred pass goes through ONE grouped launch first (real + generated),
         # with fresh parameter blocks per D step and per G step. Parameter objects without the attribute mean "off".
-        from ..functional_aug import parse_policy
+        from ..functional_aug import GEO, parse_policy
         self.aug = parse_policy(getattr(params, 'D_aug', ''))
+        self.geo = self.aug & GEO         # flip / scale / rotate: their own launch in front, one more block per site
         self._xs_g = None                 # the augmented real pyramid of G part 0 (reused by later fused G steps)
         # adaptive strength (--D_aug_p / --D_ada): each transformation applied per clip with probability p, read from
         # device memory by the gated launches. p is the controller's (gan.ada, updated behind every D forward) or a fixed value;
@@ -290,23 +297,34 @@ class TrainStep(object):
     def _augment(self, real, fake):
         """(real, fake) through the augmentation, both lists (either may be None) in one launch: a block of draws for the real
         clips first, then one for the generated clips. Under --subsample_input level l's sample j reads base row j * 2^l. Gated:
-        every block comes with its gate block, and the launch reads the current p."""
+        every block comes with its gate block, and the launch reads the current p. With a geometric name in the policy every
+        block also comes with its geometric block v, and the clips go through the resampling launch first (geometry, then colour,
+        translation, cutout)."""
         if not self.aug:
             return real, fake
-        from ..functional_aug import diffaug
-        xs, us, gs, strides = [], [], [], []
+        from ..functional_aug import diffaug, geoaug
+        xs, us, gs, vs, strides = [], [], [], [], []
         for clips in (real, fake):
             if clips is None:
                 continue
-            if self.gated:
+            g = v = None
+            if self.geo:
+                got = TF.draws.aug(self._batch, self.device, gated=self.gated, geo=True)    # u, [g], v: one after the other
+                u, v = got[0], got[-1]
+                if self.gated:
+                    g = got[1]
+            elif self.gated:
                 u, g = TF.draws.aug(self._batch, self.device, gated=True)         # the gate block right behind its parameter block
             else:
-                u, g = TF.draws.aug(self._batch, self.device), None
+                u = TF.draws.aug(self._batch, self.device)
             for l, t in enumerate(clips):
                 xs.append(t)
                 us.append(u)
                 gs.append(g)
+                vs.append(v)
                 strides.append(2 ** l if self.params.subsample_input else 1)
+        if self.geo:
+            xs = geoaug(xs, vs, strides, self.geo, gs, self._p) if self.gated else geoaug(xs, vs, strides, self.geo)
         out = diffaug(xs, us, strides, self.aug, gs, self._p) if self.gated else diffaug(xs, us, strides, self.aug)
         n = len(real) if real is not None else 0
         return (out[:n] if real is not None else None), (out[n:] if fake is not None else None)
@@ -470,7 +488,8 @@ class GraphedTrainStep(object):
                                     gp=params.gp_lambda > 0, subsample_input=params.subsample_input,
                                     n_perms=(N + 1) * len(gan.discrims) if cond_dim else 0, n_d_steps=N, n_g_steps=M,
                                     ca_dim=getattr(gan.gen, 'ca_dim', 0) if cond_dim else 0,
-                                    n_aug=(2 * N + M + 1) * (2 if self.ts.gated else 1) if self.ts.aug else 0)
+                                    n_aug=(2 * N + M + 1) * (2 if self.ts.gated else 1) if self.ts.aug else 0,
+                                    n_geo=2 * N + M + 1 if self.ts.geo else 0)
         self.x = torch.empty(batch_shape, device=device, dtype=torch.float32)
         # conditional path: the sentence code is computed outside the graphs (its sequence length varies) into a fixed buffer
         self.cond = torch.empty((batch_shape[0], cond_dim), device=device, dtype=torch.float32) if cond_dim else None
