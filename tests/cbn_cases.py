@@ -102,7 +102,7 @@ def reference(case, recipe, relu, up, fork='off', wide=False, training=True, dty
     inp = inputs(case, recipe, wide)
     _, T, s, R = CASES[case]
     ld, off = geometry(case, wide)
-    c = lambda t: t.to(dtype)
+    c = lambda t: t.to(dtype, copy=True)              # (a copy in fp32 too: requires_grad_ below must never reach the shared inputs)
     xd = c(inp['x']).requires_grad_(training)
     gd, bd = c(inp['gamma']).requires_grad_(training), c(inp['beta']).requires_grad_(training)
     td = c(inp['tab'] if tab is None else tab).requires_grad_(training)

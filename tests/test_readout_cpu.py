@@ -34,7 +34,7 @@ def test_offsets_and_width_follow_from_the_slot_list(which, width, offsets):
     assert [n for name, off, n, t in r.slots] == [1, 1, 1] + [1 if name == 'ada.p' else 6 for name in sorted(offsets, key=offsets.get)]
     name, off, n, t = r.slots[-1]
     assert r.width == width and off + n <= width < off + n + 4
-    assert all(stage is None and hbuf.numel() == width and not hbuf.is_pinned() and ev is None for stage, hbuf, ev in r.ring)
+    assert all(hbuf.numel() == width and not hbuf.is_pinned() and ev is None for hbuf, ev in r.ring)
 
 
 def test_pop_lags_one_push_and_returns_by_name():

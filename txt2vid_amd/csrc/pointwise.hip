@@ -1312,7 +1312,6 @@ __global__ __launch_bounds__(64 * NW) void lstm_step_fused_k(const float* __rest
 extern "C" int t2v_lstm_step_fused_ok(int B, int K, int C) {
     return (B >= 1 && B <= 32 && K >= 128 && (K % 128) == 0 && C >= 4 && (C % 4) == 0) ? 1 : 0;
 }
-static int lstm_waves() { static const int w = getenv("T2V_LSTM_WAVES") ? atoi(getenv("T2V_LSTM_WAVES")) : 8; return w == 4 ? 4 : 8; }
 extern "C" int t2v_lstm_pack_major(const float* wp, float* wr, int K, int C, void* st) {
     if (!wp || !wr || K < 1 || C < 4 || (C % 4) != 0) return T2V_EINVAL;
     T2V_LAUNCH(lstm_pack_major_k, dim3((unsigned)((C / 4 + 63) / 64), (unsigned)((K + 7) / 8)), dim3(256), 0, S_(st), wp, wr, K, C);
@@ -1322,13 +1321,8 @@ extern "C" int t2v_lstm_step_fused(const float* x, const float* wr, const float*
                                    float* act, int B, int K, int C, void* st) {
     if (!x || !wr || !c_prev || !h || !c_new || !act || !t2v_lstm_step_fused_ok(B, K, C)) return T2V_EINVAL;
     const dim3 grid((unsigned)(C / 4));
-    if (lstm_waves() == 4) {
-        if (K == 1024) T2V_LAUNCH((lstm_step_fused_k<256, 4>), grid, dim3(256), 0, S_(st), x, wr, bias, c_prev, h, c_new, act, B, K, C);
-        else T2V_LAUNCH((lstm_step_fused_k<0, 4>), grid, dim3(256), 0, S_(st), x, wr, bias, c_prev, h, c_new, act, B, K, C);
-    } else {
-        if (K == 1024) T2V_LAUNCH((lstm_step_fused_k<128, 8>), grid, dim3(512), 0, S_(st), x, wr, bias, c_prev, h, c_new, act, B, K, C);
-        else T2V_LAUNCH((lstm_step_fused_k<0, 8>), grid, dim3(512), 0, S_(st), x, wr, bias, c_prev, h, c_new, act, B, K, C);
-    }
+    if (K == 1024) T2V_LAUNCH((lstm_step_fused_k<128, 8>), grid, dim3(512), 0, S_(st), x, wr, bias, c_prev, h, c_new, act, B, K, C);
+    else T2V_LAUNCH((lstm_step_fused_k<0, 8>), grid, dim3(512), 0, S_(st), x, wr, bias, c_prev, h, c_new, act, B, K, C);
     return launch_status();
 }
 
@@ -1430,15 +1424,9 @@ extern "C" int t2v_lstm_step_bwd_fused(const float* gh, const float* gnext, cons
         return T2V_EINVAL;
     const int halves = (B + 15) / 16;
     const dim3 grid((unsigned)(C / 16 * halves));
-    if (lstm_waves() == 4) {
-        if (C == 1024) T2V_LAUNCH((lstm_step_bwd_fused_k<1024, 4>), grid, dim3(256), 0, S_(st), gh, gnext, w1, gc_in, act, c_prev, c_new, gpre,
-                                  gc_prev, B, C, halves);
-        else T2V_LAUNCH((lstm_step_bwd_fused_k<0, 4>), grid, dim3(256), 0, S_(st), gh, gnext, w1, gc_in, act, c_prev, c_new, gpre, gc_prev, B, C, halves);
-    } else {
-        if (C == 1024) T2V_LAUNCH((lstm_step_bwd_fused_k<1024, 8>), grid, dim3(512), 0, S_(st), gh, gnext, w1, gc_in, act, c_prev, c_new, gpre,
-                                  gc_prev, B, C, halves);
-        else T2V_LAUNCH((lstm_step_bwd_fused_k<0, 8>), grid, dim3(512), 0, S_(st), gh, gnext, w1, gc_in, act, c_prev, c_new, gpre, gc_prev, B, C, halves);
-    }
+    if (C == 1024) T2V_LAUNCH((lstm_step_bwd_fused_k<1024, 8>), grid, dim3(512), 0, S_(st), gh, gnext, w1, gc_in, act, c_prev, c_new, gpre,
+                              gc_prev, B, C, halves);
+    else T2V_LAUNCH((lstm_step_bwd_fused_k<0, 8>), grid, dim3(512), 0, S_(st), gh, gnext, w1, gc_in, act, c_prev, c_new, gpre, gc_prev, B, C, halves);
     return launch_status();
 }
 

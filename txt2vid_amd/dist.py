@@ -146,7 +146,7 @@ class GradArena(object):
     def gather(self):
         """p.grad -> arena slice (missing grads count as zero). `copy_fn` is a FLAT copy (dense source -> the destination's
         memory in order), so it only takes pairs whose memory orders agree; a dense gradient for a tap-major slot (a ConvLSTM
-        weight whose gradient bypassed the sink: --end2end, T2V_NO_DEFERRED_REDUCE, one-step sequences) goes tap row by tap row."""
+        weight whose gradient bypassed the sink: --end2end, one-step sequences) goes tap row by tap row."""
         if self.flat.is_cuda:
             from . import functional as TF
             TF.grad_sink_flush()              # pending k-split partial sums belong in the arena before anyone reads it

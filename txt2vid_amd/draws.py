@@ -10,10 +10,6 @@ import torch
 # graph reads this iteration's phases / z / alphas from the same addresses on every replay.
 # ------------------------------------------------------------------------------------------------
 
-import os as _os
-
-_UPLOAD_BY_MEMCPY = _os.environ.get('T2V_DRAWS_MEMCPY') is not None
-
 AUG_K = 8           # uniforms per sample of one augmentation block (functional_aug.K)
 
 
@@ -176,7 +172,7 @@ class StaticDraws(object):
             from .util.misc import gen_perm
             for k in range(self.n_perms):
                 self.h_perm[k].copy_(torch.from_numpy(gen_perm(self.batch).astype('int32')))
-        if self.d_all.is_cuda and not _UPLOAD_BY_MEMCPY:
+        if self.d_all.is_cuda:
             # a copy KERNEL reading the pinned buffer in place (pinned host memory is mapped into the device's address space): it
             # stays on the compute queue, where the copy engine's memcpy costs a queue hand-over each way in front of the graph
             # that reads the draws (~100 us of idle time per iteration in the text-conditioned loop, ~20 us in the unconditional one)

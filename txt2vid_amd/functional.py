@@ -78,9 +78,6 @@ def input_grads_only():
         _param_grads_enabled = old
 
 
-_NO_VEC_REDUCE = bool(os.environ.get('T2V_NO_VEC_REDUCE'))       # developer A/B switch: scalar slab loads in the batched reduce
-
-
 class _PendingDest(object):
     __slots__ = ('wid', 'bid', 'dw', 'dbias', 'CoCi', 'T', 'Cout', 'accum', 'accum_bias', 'srcs', 'keep', 'tap_major')
 
@@ -102,7 +99,6 @@ class GradSink(object):
         for arena in arenas:
             for off, p in zip(arena.offsets, arena.params):
                 self.slots[id(p)] = (arena, off, p.numel())
-        self.defer = os.environ.get('T2V_NO_DEFERRED_REDUCE') is None
         self.pending, self.pending_bias = {}, {}          # id(weight) -> _PendingDest; id(bias) -> id(weight)
         # Destination tables live in a fixed device buffer, uploaded from a fixed pinned buffer (both allocated HERE, outside
         # any graph capture): a table is uploaded once per distinct content (slot per signature) — a copy from pinned memory
@@ -111,11 +107,10 @@ class GradSink(object):
         self.slot_bytes, self.nslots = 65536, 48
         dev = arenas[0].flat.device if arenas else None
         self.tab_pin = self.tab_dev = None
-        if dev is not None and dev.type == 'cuda' and self.defer:
+        self.defer = dev is not None and dev.type == 'cuda'          # device tables exist (CPU arenas: no kernel writes them)
+        if self.defer:
             self.tab_pin = torch.empty(self.slot_bytes * self.nslots, dtype=torch.uint8).pin_memory()
             self.tab_dev = torch.empty(self.slot_bytes * self.nslots, dtype=torch.uint8, device=dev)
-        else:
-            self.defer = False
         # k-split slabs come from one bump-allocated workspace sized by the first iteration: every later iteration — eager,
         # captured or replayed — hands each launch the same address, so the destination tables repeat and are uploaded once
         self.ws, self.ws_off, self.ws_used = None, 0, 0
@@ -196,7 +191,7 @@ class GradSink(object):
             a.dw, a.dbias, a.CoCi, a.T, a.Cout = d.dw, d.dbias or None, d.CoCi, d.T, d.Cout
             a.nsrc, a.accum, a.accum_bias, a.tap_major = len(d.srcs), d.accum, d.accum_bias, d.tap_major
             smax = max(sr.S for sr in d.srcs)
-            vec = not _NO_VEC_REDUCE and d.CoCi % 4 == 0 and d.CoCi >= 1024 and all(sr.slab % 16 == 0 and sr.tap_stride % 4 == 0 and sr.split_stride % 4 == 0
+            vec = d.CoCi % 4 == 0 and d.CoCi >= 1024 and all(sr.slab % 16 == 0 and sr.tap_stride % 4 == 0 and sr.split_stride % 4 == 0
                                                              for sr in d.srcs)
             if vec:                  # 16-byte slab loads, 256 pairs per workgroup; same split between the two forms (and same
                 a.kind = 3 if (d.CoCi <= 16384 and smax >= 16) else 2          # summation order) as the scalar kinds 1 / 0
@@ -290,37 +285,30 @@ def grad_sink_flush():
         _grad_sink.flush()
 
 
-def _wgrad_to_sink(w, b, launch_partial, launch_direct):
+def _wgrad_to_sink(w, b, launch_partial):
     """Weight (and, with `b`, bias) gradient of one convolution into the sink slots of its parameters: the ONE place that
-    resolves the slots (weight first), chooses between the deferred and the immediate reduce and registers the slab.
-    `launch_partial(sink)` runs the weight-gradient main kernel alone and returns (WgradSrc, slab);
-    `launch_direct(dw, accum, dbias, accum_bias)` runs it with its reduce pass. Nothing goes to the sink while autograd records,
-    or unless every parameter asked for has a slot. Returns (handled, gw, gb) like `_to_sink`: a gradient is None once accumulated."""
+    resolves the slots (weight first) and registers the slab.
+    `launch_partial(sink)` runs the weight-gradient main kernel alone and returns (WgradSrc, slab). Nothing goes to the sink
+    while autograd records, when the sink has no device tables (CPU arenas), or unless every parameter asked for has a slot.
+    Returns (handled, gw, gb) like `_to_sink`: a gradient is None once accumulated."""
     sink = _grad_sink
-    if sink is None or w is None or torch.is_grad_enabled():
+    if sink is None or not sink.defer or w is None or torch.is_grad_enabled():
         return False, None, None
     wbase = w._base if w._base is not None else w
     if id(wbase) not in sink.slots or (b is not None and id(b) not in sink.slots):
         return False, None, None
-    deferred = sink.defer
-    wflat, wacc = sink.take(wbase, deferred)
-    bflat, bacc = sink.take(b, deferred) if b is not None else (None, False)
+    wflat, wacc = sink.take(wbase, True)
+    bflat, bacc = sink.take(b, True) if b is not None else (None, False)
     dw = wflat.view(w.shape)
-    if deferred:
-        src, slab = launch_partial(sink)
-        sink.add_partial(wbase, dw, wacc, b, bflat, bacc, src, slab, w.shape[2] * w.shape[3] * w.shape[4], w.shape[0], w.shape[0] * w.shape[1])
-    else:
-        launch_direct(dw, wacc, bflat, bacc)
+    src, slab = launch_partial(sink)
+    sink.add_partial(wbase, dw, wacc, b, bflat, bacc, src, slab, w.shape[2] * w.shape[3] * w.shape[4], w.shape[0], w.shape[0] * w.shape[1])
     return True, (None if wacc else dw), (None if b is None or bacc else bflat.view(b.shape))
 
 
 def _conv_wgrad_to_sink(w, b, xs, gys, relu_in, even_frames=False):
     """`_wgrad_to_sink` for a (grouped) convolution; with `b` the bias gradient comes out of the same launch
     (`t2v_conv_wgrad_grouped_bias`: the 3-tap-row kernel sums the dL/dy tiles it stages anyway)."""
-    return _wgrad_to_sink(
-        w, b, lambda sink: _wgrad_partial_launch(xs, gys, tuple(w.shape), relu_in, b is not None, sink, even_frames),
-        lambda dw, wacc, db, bacc: conv_group_wgrad_raw(xs, gys, tuple(w.shape), relu_in, out=dw, accum=wacc, dbias=db, accum_bias=bacc,
-                                                        even_frames=even_frames))
+    return _wgrad_to_sink(w, b, lambda sink: _wgrad_partial_launch(xs, gys, tuple(w.shape), relu_in, b is not None, sink, even_frames))
 
 
 def _to_sink(param_like, compute):
@@ -1124,7 +1112,7 @@ def _skinny_ok(M, K, N):
 
 
 def _lstm_fused_ok(B, K, Cc):
-    return os.environ.get('T2V_NO_LSTM_FUSED', '0') != '1' and bool(lib().t2v_lstm_step_fused_ok(B, K, Cc))
+    return bool(lib().t2v_lstm_step_fused_ok(B, K, Cc))
 
 
 def _skinny(x, wp, M, K, N):

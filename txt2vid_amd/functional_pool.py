@@ -11,7 +11,6 @@ also keeps the even frames only), 8x behind a (2,2,2) DownSample; identical valu
 penalty's recorded sweep and its second backward stay on these kernels. Part of the autograd surface `txt2vid_amd.functional`
 (re-exported there)."""
 import ctypes as C
-import os
 
 import torch
 from torch.autograd import Function
@@ -20,8 +19,7 @@ from torch.autograd.function import once_differentiable
 from ._lib import lib, check, ConvGroup, PoolBoxJob, WgradSrc, MAX_GROUPS
 from ._ops import _stream, _p, _c
 
-_DISABLED = os.environ.get('T2V_NO_POOLCONV') is not None        # developer A/B switch: the un-pooled path everywhere
-_NO_UPCONV = os.environ.get('T2V_NO_UPCONV') is not None         # developer A/B switch: UpBlocks up-sample, then convolve
+_DISABLED = False        # a test sets it to get the un-pooled form as its reference
 
 
 def _TF():
@@ -233,11 +231,9 @@ def _pool_wgrad_partial(sink, rts, gzs, shapes, tmodes, wshape, want_bias):
 
 
 def _pool_wgrad_to_sink(w, b, rts, gzs, shapes, tmodes):
-    """Weight (and, with `b`, bias) gradient into the gradient sink's slots (`functional._wgrad_to_sink`, which defers the
-    reduce when the sink batches its reductions). Returns (handled, gw, gb)."""
-    return _TF()._wgrad_to_sink(
-        w, b, lambda sink: _pool_wgrad_partial(sink, rts, gzs, shapes, tmodes, tuple(w.shape), b is not None),
-        lambda dw, wacc, db, bacc: pool_wgrad_raw(rts, gzs, shapes, tmodes, tuple(w.shape), out=dw, accum=wacc, dbias=db, accum_bias=bacc))
+    """Weight (and, with `b`, bias) gradient into the gradient sink's slots (`functional._wgrad_to_sink`, which leaves the
+    reduce to the sink's flush). Returns (handled, gw, gb)."""
+    return _TF()._wgrad_to_sink(w, b, lambda sink: _pool_wgrad_partial(sink, rts, gzs, shapes, tmodes, tuple(w.shape), b is not None))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -381,7 +377,7 @@ def pool_conv_group(xs, w, b=None, relu_in=True, stem=False):
 
 def up_conv_ok(x, w):
     TF = _TF()
-    return (not _DISABLED and not _NO_UPCONV and TF.CONV_PRECISION == 'fp32' and x.dim() == 4 and x.is_cuda and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)
+    return (not _DISABLED and TF.CONV_PRECISION == 'fp32' and x.dim() == 4 and x.is_cuda and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)
             and w.shape[0] % 32 == 0 and w.shape[1] % 32 == 0)
 
 

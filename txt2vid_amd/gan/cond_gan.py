@@ -2,7 +2,6 @@
 kwargs as txt2vid/gan/cond_gan.py:7-217. Scalar combinations of the per-level losses are done by the
 `scalar_*` kernels, not by ATen."""
 import numpy as np
-import os
 
 import torch
 
@@ -181,13 +180,11 @@ class CondGan(object):
             with TF.input_grads_only():
                 gs = torch.autograd.grad(outputs=outs, inputs=xhs, grad_outputs=[TF.ones_cached(o) for o in outs],
                                          create_graph=True, retain_graph=True, only_inputs=True)
-            if _GROUPED_GP and all(g.is_cuda for g in gs) and len(gs) <= 8:
-                # sum over levels and samples of ||dD/dx_hat||^2 as ONE grouped dot product (and one grouped scale + add in its
-                # adjoint) instead of a squared-norm / sum pair per level and their adjoints: the same sum in another order
-                ga, gb = TF.fork_group(list(gs))
-                gp = TF.scalar_sum([TF.dot_group(ga, gb)], weights=[self.gp_scale])
-            else:
-                gp = TF.scalar_sum([TF.vec_sum(TF.row_sqnorm(g), self.gp_scale) for g in gs])
+            # sum over levels and samples of ||dD/dx_hat||^2 as ONE grouped dot product (and one grouped scale + add in its
+            # adjoint) instead of a squared-norm / sum pair per level and their adjoints: the same sum in another order
+            # (`_fusable` admits device clips of at most MAX_GROUPS / 2 levels here: one group always takes them)
+            ga, gb = TF.fork_group(list(gs))
+            gp = TF.scalar_sum([TF.dot_group(ga, gb)], weights=[self.gp_scale])
             l = TF.scalar_sum([l, gp] + reg[0], weights=[1.0, gp_lambda] + reg[1])
         elif reg[0]:
             l = TF.scalar_sum([l] + reg[0], weights=[1.0] + reg[1])
@@ -343,9 +340,6 @@ class CondGan(object):
 
 def _can_batch(real, fake):
     return all(r.is_cuda and r.shape == f.shape for r, f in zip(real, fake))
-
-
-_GROUPED_GP = os.environ.get('T2V_NO_GROUPED_GP') is None
 
 
 def _fusable(discrim, real, fake):

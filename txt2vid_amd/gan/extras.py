@@ -20,35 +20,30 @@ def training_extras(gan, optD, optG):
 class Readout(object):
     """The losses and the extras' floats, read ONE iteration late through two pinned buffers with an event each: the host launches
     the next iteration while this one runs (a replay overwrites its loss scalars, hence the copies). One copy launch per slot: a
-    kernel writing the pinned buffer in place, or with `by_memcpy` into a device row that one memcpy brings over. CPU: plain copies."""
+    kernel writing the pinned buffer in place. CPU: plain copies."""
 
-    def __init__(self, extras, device, by_memcpy=False):
+    def __init__(self, extras, device):
         self.slots, off = [], 0                # (name, offset, floats, tensor or None: handed to `push`)
         for name, t, n in [(l, None, 1) for l in LOSSES] + [s for e in extras for s in e.slots]:
             self.slots.append((name, off, n, t))
             off += n
         self.width = -(-off // 4) * 4          # whole 16-byte rows
         self.cuda = torch.device(device).type == 'cuda'
-        self.ring = [(torch.empty(self.width, device=device) if self.cuda and by_memcpy else None,      # staging row
-                      torch.zeros(self.width).pin_memory() if self.cuda else torch.zeros(self.width),
+        self.ring = [(torch.zeros(self.width).pin_memory() if self.cuda else torch.zeros(self.width),
                       torch.cuda.Event() if self.cuda else None) for _ in range(2)]
         self.prev = self.last = None           # the ring entries of the last two pushes
 
     def push(self, k, **losses):
         """Start the copies of iteration `k`: the loss tensors by slot name (None: stays 0) and every extra's."""
-        stage, hbuf, ev = self.ring[k & 1]
+        hbuf, ev = self.ring[k & 1]
         for name, off, n, t in self.slots:
             t = losses.get(name, t)
             if t is None:
                 continue
-            if not self.cuda:
-                hbuf[off:off + n].copy_(t.reshape(-1)[:n])
-            elif stage is None:
+            if self.cuda:
                 TF._copy2d(t, 0, n, hbuf, off, n, 1, n)
             else:
-                TF.copy_into(t.reshape(-1)[:n], stage[off:off + n])
-        if stage is not None:
-            hbuf.copy_(stage, non_blocking=True)
+                hbuf[off:off + n].copy_(t.reshape(-1)[:n])
         if ev is not None:
             ev.record()
         self.prev, self.last = self.last, self.ring[k & 1]
@@ -57,7 +52,7 @@ class Readout(object):
         """{name: [floats]} of the push before the last one (waits for its event); None before there is one."""
         if self.prev is None:
             return None
-        stage, hbuf, ev = self.prev
+        hbuf, ev = self.prev
         if ev is not None:
             ev.synchronize()
         return {name: hbuf[off:off + n].tolist() for name, off, n, t in self.slots}

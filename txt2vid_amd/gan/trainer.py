@@ -16,7 +16,6 @@ block is followed, behind its gate block if there is one, by its geometric block
 v_fake at a site with both lists.
 """
 import argparse
-import os
 import sys
 
 import torch
@@ -468,10 +467,6 @@ def train_iteration(gan, x, cond, optD, optG, losses, params, device, end2end=Fa
     return TrainStep(gan, optD, optG, losses, params, device, end2end, grad_sync).run(x, cond)
 
 
-_X_BY_MEMCPY = os.environ.get('T2V_DRAWS_MEMCPY') is not None
-_DRAWS_LAST = os.environ.get('T2V_DRAWS_LAST') is not None
-
-
 class GraphedTrainStep(object):
     """HIP-graph replay of the training iteration: after `warmup` eager iterations the N + M + 1 parts of `TrainStep`
     are captured once (shared memory pool) and every later iteration is N + M + 1 graph launches + the N + M eager
@@ -517,7 +512,7 @@ class GraphedTrainStep(object):
         # while this thread captures; in the default (global) mode any such call invalidates the capture
         mode = 'thread_local'
         n_parts = self.ts.n_parts
-        if gs is None and os.environ.get('T2V_THREE_GRAPHS') is None:      # (T2V_THREE_GRAPHS: developer A/B switch)
+        if gs is None:
             # one process, no gradient exchange between the parts: the whole iteration is ONE graph (fewer replay launches)
             g1 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g1, stream=self.side, capture_error_mode=mode):
@@ -530,20 +525,19 @@ class GraphedTrainStep(object):
             if self.ts.grad_sink is not None:
                 self.ts.grad_sink.frozen += 1
             return
-        # one graph per part (shared memory pool); the exchange of the gradients the part computed sits after it
+        # data-parallel: one graph per part (shared memory pool); the exchange of the gradients the part computed sits after it
         graphs, exchanges = [], []
         for k in range(n_parts):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None, stream=self.side, capture_error_mode=mode):
                 which = self.ts.part(k, self.x, self.cond)
-                if gs is not None and which is not None:
+                if which is not None:
                     gs.pre(which)           # p.grad -> arena: captured (the replayed backward rewrites the same buffers)
             graphs.append(g)
             if which is not None:
                 exchanges.append(which)
-                if gs is not None:
-                    gs.exchange(which)
-                    gs.post(which)          # Adam (captured next) reads the arena views
+                gs.exchange(which)
+                gs.post(which)              # Adam (captured next) reads the arena views
         torch.cuda.synchronize()
         self.graphs = tuple(graphs)
         self.n_graphs = len(graphs)
@@ -571,16 +565,13 @@ class GraphedTrainStep(object):
         old = TF.draws
         TF.set_draws(self.draws)
         try:
-            if not _DRAWS_LAST:
-                self.draws.begin_step()                  # (host RNG work first: the launches below then reach the queue back to back)
-            if x.is_cuda and x.dtype == torch.float32 and x.shape == self.x.shape and not _X_BY_MEMCPY:
+            self.draws.begin_step()                      # (host RNG work first: the launches below then reach the queue back to back)
+            if x.is_cuda and x.dtype == torch.float32 and x.shape == self.x.shape:
                 TF.copy_into(x, self.x)                  # (a copy kernel: stays on the compute queue in front of the graph, see StaticDraws.begin_step)
             else:
                 self.x.copy_(x, non_blocking=True)
             if self.cond is not None:
                 TF.copy_into(cond.detach(), self.cond)
-            if _DRAWS_LAST:
-                self.draws.begin_step()
             if self.graphs is None and self.n >= self.warmup:
                 self._capture()          # the capture pass also executes nothing: replay right after
             if self.graphs is None:
@@ -727,7 +718,7 @@ def train(gan=None, num_epoch=None, dataset=None, device=None, optD=None, optG=N
     # host-bound (~1 000 launches at ~20 us of Python each)
     use_graph = not end2end and not getattr(params, 'no_graph', False) and torch.device(device).type == 'cuda'
     graphed, graphed_key, graphed_encoder = None, None, None
-    readout = Readout(extras, device, by_memcpy=_X_BY_MEMCPY) if use_graph else None
+    readout = Readout(extras, device) if use_graph else None
     for epoch in range(num_epoch):
         if params.log_period > 0:
             status('Epoch %d started' % (epoch + 1))

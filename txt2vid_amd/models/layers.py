@@ -257,8 +257,6 @@ class UpBlock(nn.Module):
         return x
 
 
-import os as _os
-SKIP_POOLS_FIRST = _os.environ.get('T2V_NO_SKIP_POOLS_FIRST') is None        # developer A/B switch (see down_block_levels)
 SKIP_POOLS_FIRST_MIN_VOXELS = 16384       # below this a block's launches are latency-bound: the two extra small launches cost more
 
 
@@ -310,7 +308,7 @@ def down_block_levels(block, xs):
     m = block.main.inner_module
     idm = block.main.identity_map
     cfgs = [downsample_cfg(x) for x in xs]
-    if SKIP_POOLS_FIRST and isinstance(idm[1], DownSample) and isinstance(m[4], DownSample) and isinstance(idm[0], Conv3d) and \
+    if isinstance(idm[1], DownSample) and isinstance(m[4], DownSample) and isinstance(idm[0], Conv3d) and \
             tuple(idm[0].weight.shape[2:]) == (1, 1, 1) and not any(any(p) for _, _, p in cfgs) and \
             sum(x.numel() // x.shape[1] for x in xs) >= SKIP_POOLS_FIRST_MIN_VOXELS and TF.pool_conv_ok(xs, m[3].weight, False):
         # Round 4: the skip path `conv1x1x1 -> DownSample` (layers.py:233-238) runs as DownSample -> conv1x1x1. A 1x1x1 convolution
