@@ -908,6 +908,39 @@ int t2v_mbstd_feat(const t2v_mbstd_member* members, int n, const float* w, int H
 int t2v_mbstd_second(const t2v_mbstd_member* members, int n, const float* w, int H, int K, int G, void* stream);
 int t2v_mbstd_weight(const t2v_mbstd_member* members, int n, float* W, int H, int K, int G, int accum, void* stream);
 
+/* ---- contrastive clip-caption matching term (XMC-GAN, Zhang et al. 2021; opt-in, Resnet3D(match=True), --D_match / --G_match;
+ *      DESIGN 32) ---------------------------------------------------------------------------------------------------------------
+ * One definition. A member has b rows: embedded features e [b, J] (= f W, computed by t2v_proj_cond) and sentence codes s [b, J].
+ *   eh_i = e_i / max(|e_i|, 1e-12)    sh_j = s_j / max(|s_j|, 1e-12)    S_ij = <eh_i, sh_j> / tau
+ *   M_ij = 1 if i == j or row s_i differs from row s_j in any fp32 bit pattern, else 0       (equal captions are no negatives)
+ *   L_i = (max_j S_ij - S_ii) + log sum_j M_ij exp(S_ij - max_j S_ij)    (max over M_ij = 1), L'_j likewise down column j
+ *   term = (1 / 2b) sum_i (L_i + L'_i)                         (exactly 0 when only the diagonal is left, b = 1 included)
+ * t2v_match_fwd, ONE workgroup that walks the members in order: writes per member coef [b, b] = C = (P_row + P_col - 2 I) /
+ *   (2 b tau), P_row / P_col the masked row / column softmaxes, and norms [2b] = { 1 / |e_i|, or 0 where |e_i| <= 1e-12 ;
+ *   1 / max(|s_j|, 1e-12) }; out (one float) = the mean of the members' terms; stats [4] = { out, the share of rows i of member 0
+ *   with S_ii > S_ij for every j != i with M_ij = 1, the same down the columns, the number of entries M_ij = 0 of member 0 }.
+ * t2v_match_bwd, one workgroup per (member, row), g = dL/dout (one float in DEVICE memory), scale = the weight of a member's term
+ *   in out (1 / n of the forward launch; the backward may run over fewer members): with dEh = g scale C Sh,
+ *   de_i = (dEh_i - eh_i <eh_i, dEh_i>) / |e_i|, and exactly 0 where |e_i| <= 1e-12. s gets no gradient. Reads e, s, coef, norms.
+ * `members` is a HOST array whose descriptors travel by value in the kernel arguments; all members share J. fp32; every sum
+ * runs in a fixed order (register tiles, lane butterflies, per-wave partials added in wave order): plain vector stores, no
+ * atomics, no workspace, the same bits run to run. Outputs must not alias inputs. Neither allocates or synchronises; both can
+ * be captured. T2V_EINVAL, before any launch, on members == NULL, n outside 1..T2V_MAX_GROUPS, J outside 1..T2V_MATCH_MAX_COLS,
+ * a member with b outside 1..T2V_MATCH_MAX_ROWS or a NULL e, s, coef or norms (bwd: or de), a tau that is not positive and
+ * finite, a scale outside (0, 1], or stats, out or g == NULL. */
+#define T2V_MATCH_MAX_ROWS 128
+#define T2V_MATCH_MAX_COLS 1024
+typedef struct t2v_match_member {
+    const float* e;      /* [b, J] */
+    const float* s;      /* [b, J] */
+    float* coef;         /* [b, b]: written by fwd, read by bwd */
+    float* norms;        /* [2b]: written by fwd, read by bwd */
+    float* de;           /* bwd: [b, J] written; fwd: unused */
+    int32_t b, reserved;
+} t2v_match_member;
+int t2v_match_fwd(const t2v_match_member* members, int n, int J, float tau, float* stats, float* out, void* stream);
+int t2v_match_bwd(const t2v_match_member* members, int n, int J, float scale, const float* g, void* stream);
+
 /* ---- Gram sums of the Kernel Inception Distance estimator (Binkowski et al. 2018; opt-in evaluation, --eval_period) ----
  * One definition. X (real) and Y (generated) are dense fp32 [n, d] feature matrices; with a block size s (n % s == 0, nb = n / s)
  * rows [b*s, (b+1)*s) of X and of Y form block b, and with k(u, v) = (alpha u.v + 1)^3

@@ -120,6 +120,13 @@ class MbstdMember(C.Structure):
                 ('stat', C.c_void_p), ('out', C.c_void_p), ('b', C.c_int32), ('seg', C.c_int32)]
 
 
+class MatchMember(C.Structure):
+    """t2v_match_member (include/t2v_hip.h)."""
+    _fields_ = [('e', C.c_void_p), ('s', C.c_void_p), ('coef', C.c_void_p), ('norms', C.c_void_p), ('de', C.c_void_p), ('b', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+MATCH_MAX_ROWS, MATCH_MAX_COLS = 128, 1024
 MAX_GROUPS = 8
 _P = C.c_void_p
 _I = C.c_int
@@ -290,6 +297,8 @@ SIGNATURES = {
     't2v_mbstd_feat': [_P, _I, _P, _I, _I, _I, _P],
     't2v_mbstd_second': [_P, _I, _P, _I, _I, _I, _P],
     't2v_mbstd_weight': [_P, _I, _P, _I, _I, _I, _I, _P],
+    't2v_match_fwd': [_P, _I, _I, _F, _P, _P, _P],
+    't2v_match_bwd': [_P, _I, _I, _F, _P, _P],
     't2v_kid_sums': [_P, _P, _I, _I, _I, C.c_double, _P, _P, _P],
     't2v_kid_sums_ws_bytes': [_I, _I, _I],
     't2v_knn_radii': [_P, _I, _I, _I, _P, _P, _P],

@@ -2765,6 +2765,8 @@ from .functional_pool import (pool_conv_ok, pool_conv_group, pool_tmode, PoolCon
 # the projection head of the text-conditioned discriminator (opt-in): functional_proj.py
 from .functional_proj import (_scatter, proj_rows_group, proj_rows_raw, proj_feat_raw, proj_cond_raw, proj_weight_raw, ProjRowsG, ProjFeatG,     # noqa: E402,F401
                               ProjCondG, ProjWeightG)
+# the contrastive clip-caption matching term of the text-conditioned discriminator (opt-in): functional_match.py
+from .functional_match import MATCH_MAX_ROWS, MATCH_MAX_COLS, match_group, match_embedded, match_fwd_raw, match_bwd_raw, MatchG     # noqa: E402,F401
 # the minibatch standard deviation head of the discriminator (opt-in): functional_mbstd.py
 from .functional_mbstd import check_group as mbstd_check_group  # noqa: E402,F401
 from .functional_mbstd import (mbstd_group, mbstd_fwd_raw, mbstd_feat_raw, mbstd_second_raw, mbstd_weight_raw, MbstdFwdG, MbstdFeatG,     # noqa: E402,F401

@@ -39,6 +39,7 @@ class CondGan(object):
         self.discrim_sn = None            # gan.spectral.SpectralNorm of `discrims` (--D_sn, not in the reference), or None
         self.ada = None                   # gan.ada.AdaState, the controller of the augmentation's p (--D_ada, not in the reference), or None
         self.lecam = None                 # gan.lecam.LeCamState, the anchors of the LeCam term (--D_lecam, not in the reference), or None
+        self.match = None                 # gan.match.MatchState, the clip-caption matching term (--D_match / --G_match, not in the reference), or None
         self.kid = None                   # gan.kid.KidEvaluator (--eval_period, not in the reference), or None: in no checkpoint
 
     def _observe(self, discrim, u_r, u_f):
@@ -58,6 +59,17 @@ class CondGan(object):
         n = len(u_r)
         mine, its = TF.fork_group(list(u_r) + list(u_f))
         return mine[:n], mine[n:], ([self.lecam.term(its[:n], its[n:])], [self.lecam.lam])
+
+    def _match_head(self, discrim, side):
+        """--D_match / --G_match: the matching head of the first discriminator when this side's term is on, else None."""
+        m = self.match
+        if m is None or discrim is not self.discrims[0] or (m.lam_d if side == 'D' else m.lam_g) is None:
+            return None
+        from .match import head_of
+        head = head_of(discrim)
+        if head is None:
+            raise ValueError('the matching term needs a discriminator built with match=True')
+        return head
 
     def _discrim_weighted_sum(self, losses, kl=None, kl_coeff=0.0):
         """cond_gan.py:26-31: mean over discriminators, or lambda-weighted sum. `kl`: the generator's conditioning-augmentation
@@ -81,14 +93,21 @@ class CondGan(object):
             real_cc = discrim(x=real, cond=real_cond, xbar=None)
             real_pred = real_cc
             if loss is not None:
+                feats_ic = [r[2] for r in real_cc]
+                head = self._match_head(discrim, 'D')
+                if head is not None:
+                    # the real clips' features gain a consumer: a grouped fork, so that one launch sums their gradients
+                    feats_ic, feats_m = TF.fork_group(feats_ic)
+                    reg = ([self.match.term(head, feats_m, real_cond, 'D')], [self.match.lam_d])
                 # D(real, mismatched captions): only the conditional head differs from real_cc, so its
                 # trunk features are reused (the reference *means* to — it passes computed_features,
                 # cond_gan.py:45-48 — but recomputes them, tganv2_cond/discrim.py:35,40-41; same values).
-                real_ic = [discrim.sub_discrims[i](cond=fake_cond[i], computed_features=real_cc[i][2])
+                real_ic = [discrim.sub_discrims[i](cond=fake_cond[i], computed_features=feats_ic[i])
                            for i in range(len(real))] if hasattr(discrim, 'sub_discrims') else \
                     discrim(x=real, cond=fake_cond, xbar=None)
                 fake_cc = discrim(x=fake, cond=real_cond, xbar=None)
-                u_r, u_f, reg = self._lecam(discrim, [r[0] for r in real_cc], [f[0] for f in fake_cc])
+                u_r, u_f, reg_l = self._lecam(discrim, [r[0] for r in real_cc], [f[0] for f in fake_cc])
+                reg = (reg_l[0] + reg[0], reg_l[1] + reg[1])
                 lu = TF.scalar_mean([loss(fake=f, real=r) for f, r in zip(u_f, u_r)])
                 self._observe(discrim, [r[0] for r in real_cc], [f[0] for f in fake_cc])
                 l1 = TF.scalar_mean([loss(fake=f[1], real=r[1]) for f, r in zip(fake_cc, real_cc)])
@@ -156,10 +175,19 @@ class CondGan(object):
             # D(real, mismatched captions): second head on the real half's trunk features
             trunk = discrim.sub_discrims
             shared = trunk[0].module if hasattr(trunk[0], 'module') and not hasattr(trunk[0], 'cond_heads') else trunk[0]
+            head = self._match_head(discrim, 'D')
             if all(t is trunk[0] for t in trunk) and hasattr(shared, 'cond_heads'):
                 # one shared trunk: the mismatched-caption heads of every level in two launches
-                c_ic = shared.cond_heads(TF.head_rows_group([both[i][2] for i in range(n)], b), list(fake_cond))
+                feats_r = TF.head_rows_group([both[i][2] for i in range(n)], b)
+                if head is not None:
+                    # the real half's features gain a consumer, the matching term with the real captions: a grouped fork, so
+                    # that one launch sums their gradients
+                    feats_r, feats_m = TF.fork_group(feats_r)
+                    reg = (reg[0] + [self.match.term(head, feats_m, real_cond, 'D')], reg[1] + [self.match.lam_d])
+                c_ic = shared.cond_heads(feats_r, list(fake_cond))
             else:
+                if head is not None:
+                    raise ValueError('the matching term needs the shared trunk (single_discrim=True)')
                 c_ic = [trunk[i](cond=fake_cond[i], computed_features=TF.head_rows(both[i][2], b[i]))[1] for i in range(n)]
             lu = _mean_over_levels(loss, u_f, u_r)
             c_r1, c_r2 = TF.fork_group(list(c_r))          # the real logits enter two loss terms: one launch sums their gradients
@@ -219,7 +247,13 @@ class CondGan(object):
             else:
                 lu = _mean_over_levels(loss, [ff[0] for ff in fk], [rr[0].detach() for rr in rl])
                 lc = _mean_over_levels(loss, [ff[1] for ff in fk], [rr[1].detach() for rr in rl])
-                losses.append(TF.scalar_sum([lc, lu], weights=[0.5, 0.5]))
+                head = self._match_head(discrim, 'G')
+                if head is not None:
+                    # the generated clips' features with their captions, through the frozen D: only df flows
+                    lm = self.match.term(head, [ff[2] for ff in fk], cond, 'G')
+                    losses.append(TF.scalar_sum([lc, lu, lm], weights=[0.5, 0.5, self.match.lam_g]))
+                else:
+                    losses.append(TF.scalar_sum([lc, lu], weights=[0.5, 0.5]))
         return self._discrim_weighted_sum(losses, kl, kl_coeff)
 
     def can_fuse_gen_step(self, fake, real):
@@ -250,7 +284,12 @@ class CondGan(object):
             else:
                 lu = TF.scalar_mean([loss(fake=ff[0], real=rr[0]) for ff, rr in zip(fake_cc, r)])
                 lc = TF.scalar_mean([loss(fake=ff[1], real=rr[1]) for ff, rr in zip(fake_cc, r)])
-                losses.append(TF.scalar_sum([lc, lu], weights=[0.5, 0.5]))
+                head = self._match_head(discrim, 'G')
+                if head is not None:
+                    lm = self.match.term(head, [ff[2] for ff in fake_cc], cond, 'G')
+                    losses.append(TF.scalar_sum([lc, lu, lm], weights=[0.5, 0.5, self.match.lam_g]))
+                else:
+                    losses.append(TF.scalar_sum([lc, lu], weights=[0.5, 0.5]))
         return self._discrim_weighted_sum(losses, kl, kl_coeff)
 
     def all_discrim_forward(self, fake=None, real=None, cond=None, loss=None, gp_lambda=-1):
@@ -324,6 +363,8 @@ class CondGan(object):
                     d.refuse_proj_mismatch(to_load[name])          # (before the key matching, which keeps the wanted keys only)
                 if hasattr(d, 'refuse_mbstd_mismatch'):
                     d.refuse_mbstd_mismatch(to_load[name])
+                if hasattr(d, 'refuse_match_mismatch'):
+                    d.refuse_match_mismatch(to_load[name])
                 d.load_state_dict(_match_keys(to_load[name], d.state_dict().keys()))
         if self.gen_ema is not None:
             # a file without the key (written without --G_ema, or by the reference) leaves the average a copy of the loaded `gen`;

@@ -1,4 +1,4 @@
-"""The seam between `train()` and the features that log or travel with the losses: AdaState, LeCamState, LrSchedule, GradGuard carry
+"""The seam between `train()` and the features that log or travel with the losses: AdaState, LeCamState, MatchState, LrSchedule, GradGuard carry
     slots                            [(name, fp32 device tensor, leading floats of it)] to read with the losses
     key                              the checkpoint key train() writes its `state_dict()` under, or None (CondGan.save_dict has ada's and lecam's)
     log_lines(iteration, values)     its lines of the log block; `values`: {name: [floats]} of every slot read so far"""
@@ -10,11 +10,11 @@ LOSSES = ('lD', 'lG', 'kl')          # the loss slots in front of the extras' (k
 
 
 def training_extras(gan, optD, optG):
-    """The extras of a run in the order of their log lines: ada, lecam, lr schedule, guard. Call it when train() starts."""
+    """The extras of a run in the order of their log lines: ada, lecam, match, lr schedule, guard. Call it when train() starts."""
     sched, guard = optD.lr_sched and optD.lr_sched.sched, optD.grad_guard and optD.grad_guard.guard
     if sched is not None:
         sched.it0 = sched.counters()['D'] // sched.spi['D']       # its log counts on from where the device state stands now
-    return [e for e in (gan.ada, getattr(gan, 'lecam', None), sched, guard) if e is not None]
+    return [e for e in (gan.ada, getattr(gan, 'lecam', None), getattr(gan, 'match', None), sched, guard) if e is not None]
 
 
 class Readout(object):

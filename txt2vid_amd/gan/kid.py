@@ -37,7 +37,7 @@ from ..util.log import status
 FEATURE_SEED = 20181                  # the random feature network's seed: a constant of the code, never the run's --seed
 LATENT_SEED = 20182                   # the M latents (and conditioning-augmentation eps) of every evaluation
 FEATURE_INIT = 'xavier'
-HEAD_KEYS = ('fc_uncond.', 'fc.', 'proj.', 'mbstd.')
+HEAD_KEYS = ('fc_uncond.', 'fc.', 'proj.', 'mbstd.', 'match.')
 METRICS_FILE = 'metrics.jsonl'
 
 

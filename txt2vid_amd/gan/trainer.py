@@ -70,7 +70,7 @@ def _positive(kind, flag):
 def add_params_to_parser(parser):
     """Flag-for-flag txt2vid/gan/trainer.py:15-42 (including the `store_false` quirk of --no_mean_*); --no_graph, --G_ema,
     --G_ema_start, --D_aug, --D_aug_p, --D_ada, --D_ada_interval, --D_ada_kclips, --D_lecam, --D_lecam_decay, --D_lecam_start,
-    --D_sn, --lr_decay, --lr_decay_iters, --lr_decay_start, --lr_final, --grad_guard, --D_clip, --G_clip, --eval_period,
+    --D_sn, --D_match, --G_match, --match_tau, --lr_decay, --lr_decay_iters, --lr_decay_start, --lr_final, --grad_guard, --D_clip, --G_clip, --eval_period,
     --eval_clips, --eval_block, --eval_net and --eval_prdc are new."""
     parser.add_argument('--data_is_imgs', action='store_true', default=False)
     parser.add_argument('--img_model', action='store_true', default=False)
@@ -129,6 +129,18 @@ def add_params_to_parser(parser):
     parser.add_argument('--D_sn', action='store_true', default=False,
                         help='(new) spectral normalisation of every Conv3d / Linear weight of the discriminators: one power '
                              'iteration after each discriminator update')
+    parser.add_argument('--D_match', type=_positive(float, '--D_match'), default=None, metavar='LAMBDA',
+                        help='(new) contrastive clip-caption matching (XMC-GAN, Zhang et al. 2021): add LAMBDA > 0 times a symmetric '
+                             "InfoNCE loss between the discriminator's embedded features of the real clips and their sentence "
+                             'codes to the D loss; every other caption of the batch is a negative, equal captions are masked. '
+                             'Needs match=True in the --D spec (tools/cfg/discrim_cond_match.json); one discriminator, not with '
+                             "--end2end. XMC-GAN uses 1.0 on images: nobody has tuned it for video")
+    parser.add_argument('--G_match', type=_positive(float, '--G_match'), default=None, metavar='LAMBDA',
+                        help='(new) add LAMBDA > 0 times the same loss of the generated clips with their captions, through the '
+                             'frozen discriminator, to the G loss (same requirements as --D_match; either or both). Alone, nothing trains '
+                             'the head: G is then trained against its fixed initial random projection, or a loaded one')
+    parser.add_argument('--match_tau', type=float, default=None, metavar='TAU',
+                        help="(new) temperature of --D_match / --G_match (default 0.1, XMC-GAN's value for images; untuned here)")
     parser.add_argument('--lr_decay', choices=('none', 'linear', 'cosine'), default='none',
                         help='(new) decay --G_lr and --D_lr by one factor per training iteration, inside the replayed graph: '
                              'linear or cosine from 1 at --lr_decay_start to --lr_final at --lr_decay_iters. '
@@ -243,6 +255,9 @@ class TrainStep(object):
             sch = getattr(opt, 'lr_sched', None)
             if sch is not None and sch.spi != n:
                 raise ValueError('the learning-rate schedule counts %d optimiser steps per iteration, %s is %d' % (sch.spi, flag, n))
+        # the clip-caption matching term (--D_match / --G_match) forms no caption gradient
+        if getattr(gan, 'match', None) is not None and end2end:
+            raise NotImplementedError('--D_match / --G_match with --end2end: the term forms no caption gradient')
         self._fused = False
         self._one = None                  # dL/dL = 1 for both backward passes: one persistent 0-d tensor (no fill launch per pass)
         # the store_false quirk of --no_mean_*_loss (trainer.py:236-237,260-261): the loss of every step is divided by the step

@@ -15,6 +15,12 @@ _MBSTD_MISMATCH = ('discriminator checkpoint %s minibatch standard deviation hea
                    'built with mbstd=%s: pass the same mbstd in the --D spec')
 
 
+_MATCH_MISMATCH = ('discriminator checkpoint %s matching head (match.weight key) but this discriminator was built with match=%s: '
+                   'pass the same match in the --D spec')
+
+MATCH_SEED = 0x6d617463           # the draws of every matching head's initial W: a generator of its own under this constant
+
+
 class MinibatchStd(nn.Module):
     """The weight of the minibatch standard deviation head (`Resnet3D(mbstd=G)`, Karras et al. 2018; not in the reference). One
     definition (functional_mbstd.py): rows [i·seg, (i+1)·seg) of the features f [b, K] form a segment (seg = b unless stated),
@@ -52,15 +58,41 @@ class CondProjection(nn.Module):
         return TF.proj_rows_group(self.weight, feats, conds, bases)
 
 
+class CondMatch(nn.Module):
+    """The weight of the matching head (`Resnet3D(match=True)`, XMC-GAN, Zhang et al. 2021; not in the reference): `weight` = W
+    [in_ch, cond_dim] embeds the trunk's features next to the sentence codes for the contrastive clip-caption term of
+    `--D_match` / `--G_match` (functional_match.py). The head never feeds a logit: a match discriminator outputs what the plain
+    one outputs, bit for bit. W cannot start at zero (the cosine has no gradient direction there): it is drawn as N(0, 1/in_ch)
+    from a torch.Generator of its own under MATCH_SEED, and `init()` walks past this class without drawing, so every other
+    layer's host draws are unchanged. Not an nn.Linear: `--D_sn` leaves W alone. `ones` (not in the state dict) is the constant
+    vector the embedding launch takes as its row weights: made here, outside any graph capture."""
+
+    def __init__(self, in_features, cond_dim):
+        super().__init__()
+        g = torch.Generator()
+        g.manual_seed(MATCH_SEED)
+        self.weight = nn.Parameter(torch.randn(int(in_features), int(cond_dim), generator=g) * (1.0 / int(in_features)) ** 0.5)
+        self.register_buffer('ones', torch.ones(TF.MATCH_MAX_ROWS), persistent=False)
+
+    def forward(self, feats, conds, tau, stats, frozen=False):
+        """The mean over the members of the matching term of (feats[i] @ W, conds[i]) as a 0-d tensor: two launches. `frozen`:
+        W is a constant of this call (the G step, where D's parameters get no gradient)."""
+        return TF.match_group(self.weight.detach() if frozen else self.weight, feats, conds, tau, stats, ones=self.ones)
+
+
 class Resnet3D(nn.Module):
 
     def __init__(self, num_channels=1, mid_ch=64, which_conv=None, which_pool=None, cond_dim=0, num_down_blocks=4,
-                 wide=False, with_attn=True, proj=False, mbstd=0):
+                 wide=False, with_attn=True, proj=False, mbstd=0, match=False):
         super().__init__()
         # proj: the conditional logit gains the bilinear term featᵀ V s of a projection discriminator (functional_proj.py; not in
         # the reference, off by default). proj = False builds exactly the reference's module.
         if proj and cond_dim < 1:
             raise ValueError('proj (projection head) needs a sentence code (cond_dim > 0): it cannot run with --dont_use_sent')
+        # match: the head of the contrastive clip-caption matching term (CondMatch above; not in the reference, off by default).
+        # match = False builds exactly the reference's module.
+        if match and cond_dim < 1:
+            raise ValueError('match (matching head) needs a sentence code (cond_dim > 0): it cannot run with --dont_use_sent')
         # mbstd: group size G of the minibatch standard deviation head (MinibatchStd above; not in the reference); 0 = off builds
         # exactly the reference's module.
         if mbstd != 0:
@@ -86,6 +118,8 @@ class Resnet3D(nn.Module):
             self.proj = CondProjection(in_ch, cond_dim)           # registered after fc: one trailing state-dict key
         if mbstd:
             self.mbstd = MinibatchStd(mbstd, 2 if cond_dim > 0 else 1)        # registered last: one trailing state-dict key
+        if match:
+            self.match = CondMatch(in_ch, cond_dim)               # registered last of all: one trailing state-dict key
 
     def groupable(self):
         m = self.res_block.inner_module
@@ -220,6 +254,9 @@ class Resnet3D(nn.Module):
         has = 'mbstd.weight' in state_dict
         if has != hasattr(self, 'mbstd'):
             raise ValueError(_MBSTD_MISMATCH % ('has' if has else 'has no', self.mbstd.group if hasattr(self, 'mbstd') else 0))
+        has = 'match.weight' in state_dict
+        if has != hasattr(self, 'match'):
+            raise ValueError(_MATCH_MISMATCH % ('has' if has else 'has no', hasattr(self, 'match')))
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def forward(self, x=None, cond=None, xbar=None, computed_features=None, seg=None):

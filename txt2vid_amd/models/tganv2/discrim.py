@@ -2,7 +2,7 @@
 txt2vid/models/tganv2/discrim.py:7-31 (state_dict keys `single_discrim.*`)."""
 import torch.nn as nn
 
-from ..resnet3d import Resnet3D, _PROJ_MISMATCH, _MBSTD_MISMATCH
+from ..resnet3d import Resnet3D, _PROJ_MISMATCH, _MBSTD_MISMATCH, _MATCH_MISMATCH
 from ... import functional as TF
 
 
@@ -10,7 +10,7 @@ class MultiScaleDiscrim(nn.Module):
     _wrap = False
 
     def __init__(self, discrim_down_blocks=[4, 4, 4, 4], num_channels=3, cond_dim=0, underlying_discrim=Resnet3D,
-                 single_discrim=True, proj=False, mbstd=0):
+                 single_discrim=True, proj=False, mbstd=0, match=False):
         super().__init__()
         # proj: the projection head of every underlying discriminator (models/resnet3d.py; not in the reference, off by default)
         self.proj_on = bool(proj)
@@ -25,6 +25,18 @@ class MultiScaleDiscrim(nn.Module):
         self.mbstd_on = TF.mbstd_check_group(mbstd) if mbstd != 0 else 0
         if self.mbstd_on:
             extra['mbstd'] = self.mbstd_on
+        # match: the head of the contrastive clip-caption matching term (--D_match / --G_match; models/resnet3d.py; not in the
+        # reference, off by default). It feeds no logit; works together with proj and mbstd. One shared trunk only.
+        self.match_on = bool(match)
+        if self.match_on and not self._wrap:
+            raise ValueError('match (matching head) needs the text-conditioned discriminator '
+                             'txt2vid.models.tganv2_cond.discrim.MultiScaleDiscrim')
+        if self.match_on and cond_dim < 1:
+            raise ValueError('match (matching head) needs a sentence code (cond_dim > 0): it cannot run with --dont_use_sent')
+        if self.match_on and not single_discrim:
+            raise ValueError('match (matching head) needs the shared trunk (single_discrim=True): one W for every pyramid level')
+        if self.match_on:
+            extra['match'] = True
         if single_discrim:
             d = underlying_discrim(cond_dim=cond_dim, num_down_blocks=discrim_down_blocks[-1], num_channels=num_channels, **extra)
             self.single_discrim = _ModuleWrap(d) if self._wrap else d
@@ -50,9 +62,21 @@ class MultiScaleDiscrim(nn.Module):
         if has != bool(self.mbstd_on):
             raise ValueError(_MBSTD_MISMATCH % ('has' if has else 'has no', self.mbstd_on))
 
+    def refuse_match_mismatch(self, state_dict):
+        """Likewise for the matching head (`*.match.weight` keys) and match=True."""
+        has = any(k.endswith('match.weight') for k in state_dict)
+        if has != self.match_on:
+            raise ValueError(_MATCH_MISMATCH % ('has' if has else 'has no', self.match_on))
+
+    def match_head(self):
+        """The shared trunk's CondMatch module, or None."""
+        trunk = self.single_discrim.module if isinstance(self.single_discrim, _ModuleWrap) else self.single_discrim
+        return getattr(trunk, 'match', None)
+
     def load_state_dict(self, state_dict, strict=True, **kw):
         self.refuse_proj_mismatch(state_dict)
         self.refuse_mbstd_mismatch(state_dict)
+        self.refuse_match_mismatch(state_dict)
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def forward(self, x=None, cond=None, xbar=None, computed_features=None, segs=None):

@@ -61,13 +61,14 @@ def construct(args, continue_draws=True):
     the stand-alone evaluation (gan/kid.py) builds its models through here too — with `continue_draws=False`, which leaves the
     host generators where a fresh run under --seed has them instead of continuing the checkpoint's draw sequence, so that its
     loader yields the clips the run's first iterations saw."""
-    from ..gan import ada, grad_guard, kid, lecam, lr_sched
+    from ..gan import ada, grad_guard, kid, lecam, lr_sched, match
     from ..gan.ema import GenAverage
     from ..gan.spectral import check_flags, check_checkpoint, SpectralNorm, attach
     # the flags' rules are checked before a process group forms (a data-parallel start with --D_ada is refused here)
     check_flags(args)
     ada.check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
     lecam.check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
+    match.check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')))
     lr_sched.check_args(args)
     grad_guard.check_args(args)
     kid.check_args(args, world=int(os.environ.get('WORLD_SIZE', '1')),
@@ -100,6 +101,8 @@ def construct(args, continue_draws=True):
     cond_dim = txt_encoder.encoder.encoding_size if txt_encoder is not None else 0
     gen = _model(args.G, args, kind='G', cond_dim=cond_dim)
     discrims = [_model(d, args, cond_dim=cond_dim) for d in args.D]
+    # (the flags need the matching head of the --D spec; a training run refuses a head without flags in main())
+    match.check_discrims(args, discrims, training=False)
     init(gen, init_method=args.init_method)
     for d in discrims:
         init(d, init_method=args.init_method)
@@ -139,6 +142,11 @@ def construct(args, continue_draws=True):
         gan.lecam = lecam.LeCamState(args.D_lecam, args.D_lecam_decay, args.D_lecam_start, device)
         status('LeCam regularisation of the discriminator: weight %g, anchor decay %g, from D step %d (0.3 is the paper\'s value for '
                'images, untuned for video)' % (args.D_lecam, args.D_lecam_decay, args.D_lecam_start))
+    if match.enabled(args):
+        # (no state beyond the head's W, which is a parameter of the discriminator)
+        gan.match = match.MatchState(args.D_match, args.G_match, args.match_tau, device)
+        status('Clip-caption matching term: D weight %s, G weight %s, temperature %g (XMC-GAN\'s values for images, untuned for '
+               'video)' % (args.D_match, args.G_match, args.match_tau))
     if args.weights is not None:
         to_load = torch.load(args.weights, map_location=device, weights_only=False)
         check_checkpoint(to_load, args.D_sn, args.weights)
@@ -234,6 +242,9 @@ def main(args):
     c = construct(args)
     gan, optD, optG, losses, dataset, device, vocab, grad_sync = (c[k] for k in ('gan', 'optD', 'optG', 'losses', 'dataset', 'device',
                                                                                  'vocab', 'grad_sync'))
+    if not args.test:
+        from ..gan import match
+        match.check_discrims(args, gan.discrims)          # a matching head that no flag trains is refused before the loop
     if args.test:
         test(gan=gan, num_samples=args.num_samples, dataset=dataset, device=device, params=args,
              channel_first=not args.sequence_first, vocab=vocab)
